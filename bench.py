@@ -1,10 +1,25 @@
 #!/usr/bin/env python
 """Benchmark of the SBMC hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload model|splat]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload model|splat|infer] [--dump-outputs DIR] [--full]
 
 Prints ONE JSON line (rank 0).  Metric (BASELINE.json): Msamples/s = S*H*W / time for the
 denoiser's forward+backward at 1280x720, 8 spp, 21x21 kernels, fp32, inputs resident in HBM.
+
+A plain run does what that figure needs and no more: set-up, W warm-up steps, K timed steps (`ms_per_step` = the
+timed region / K), the outputs of the last timed step into DIR with --dump-outputs, the line.  Everything else the
+line can carry takes runs of its own and sits behind --full: the same step on the fp32 matrix pipe, the forward-only
+matrix, the splat stages, the instrumented steps behind the per-layer and per-rank figures, the CPU baseline and the
+parity against it (--no-stages / --no-cpu-baseline take their parts out of a --full run again).
+
+--dump-outputs DIR: what a caller of the timed step receives from the LAST timed step, as DIR/<name>.npy (float32;
+at most 64 MB in all: an array over its share is cut down to a fixed, seeded sample of its elements).  Model and
+inputs are seeded, so two builds of the package can be compared array for array under the same arguments.
+    model   radiance (the denoised image), loss, grads (the clipped parameter gradients, one flat vector)
+    infer   radiance
+    splat   radiance, d_radiance, d_logits (the gradients of all samples, one flat vector each)
+With --gpus N the arrays are rank 0's: its slab of the image, the all-reduced gradients -- and no radiance for the
+model workload, whose sharded training step hands its caller the loss only.
 
 Workloads
   model  (default; BASELINE.json configs[2], the configuration the metric is quoted on)
@@ -17,7 +32,7 @@ Workloads
   splat  one step = S progressive splat updates (ProgressiveKernelApply(splat=True), one per
          sample) + normalisation sum_r/(sum_w+eps) + backward to logits and radiance
          (SURVEY.md section 8d metric (i)): the part of the step the HIP kernels replace.
-         With the default workload this is also measured, after the timed region, and
+         With the default workload and --full this is also measured, after the timed region, and
          reported under "stages" together with the roofline figure of its dominant kernel.
 
 Multi-GPU (--gpus N): ONE frame, split along H into N slabs (strong scaling), one process per
@@ -141,9 +156,18 @@ def parse():
                     help="informational (BASELINE configs[4]): run the network under torch.autocast(float16) "
                          "(infer, or the single-GPU training step); splat arithmetic stays fp32. Never the "
                          "fp32 metric.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stages", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: fp32-pipe step, forward-only matrix, splat stages, "
+                         "per-layer and per-rank figures, CPU baseline and parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-stages", action="store_true", help="with --full: leave the stages after the timed region out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (with --gpus N: rank 0's; "
+                         "names per workload in the module docstring)")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(n):
@@ -167,10 +191,11 @@ def make_splat_inputs(h, w, spp, k, device, seed):
     g = th.Generator(device="cpu").manual_seed(seed)
     rad = [th.empty(1, 3, h, w).exponential_(1.0, generator=g).to(device).requires_grad_()
            for _ in range(spp)]
+    gd = th.Generator(device=device).manual_seed(seed)     # (drawn on the device: 1.6 GB per sample at 720p)
     logits = []
     for _ in range(spp):
         t = th.empty(1, k * k, h, w, device=device)
-        t.normal_(0, 1)
+        t.normal_(0, 1, generator=gd)
         logits.append(t.requires_grad_())
     d_out = th.randn(1, 3, h, w, generator=g).to(device)
     return rad, logits, d_out
@@ -219,15 +244,46 @@ def make_model_inputs(h, w, spp, device, seed, rows=None):
 ROW_BLOCK = 8
 
 
-def train_step(model, opt, loss_fn, batch, fp16=False):
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor, or list of tensors read as one flat vector} -> path/<name>.npy, float32.  The arrays
+    share DUMP_BYTES equally; one over its share is cut down to a sample of its elements (seeded: the same elements in every
+    run, in ascending order), gathered tensor by tensor: a list is never concatenated as a whole (13 GB of logit gradients in
+    the splat workload at 720p)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // 4 // len(arrays)
+    for name, v in arrays.items():
+        tensors = [t.detach() for t in (v if isinstance(v, (list, tuple)) else [v])]
+        total = sum(t.numel() for t in tensors)
+        if total > cap:
+            g = th.Generator(device="cpu").manual_seed(4321)
+            idx = th.randint(total, (cap,), generator=g).sort().values
+            ends = th.tensor([t.numel() for t in tensors]).cumsum(0)
+            cuts = [0] + th.searchsorted(idx, ends).tolist()       # idx[cuts[i]:cuts[i + 1]] falls into tensor i
+            tensors = [t.reshape(-1)[(idx[lo:hi] - (end - t.numel())).to(t.device)]
+                       for t, lo, hi, end in zip(tensors, cuts[:-1], cuts[1:], ends.tolist())]
+        out = tensors[0] if len(tensors) == 1 else th.cat([t.reshape(-1) for t in tensors])
+        np.save(os.path.join(path, name + ".npy"), out.float().cpu().numpy())
+
+
+def grads_of(tensors):
+    return [t.grad for t in tensors if t.grad is not None]
+
+
+def train_step(model, opt, loss_fn, batch, fp16=False, keep=None):
     """The reference training step, sbmc/interfaces.py:78-105.  fp16 (informational, never the fp32
     metric): the network runs under torch.autocast(float16) -- half activations end to end, fp32 splat
-    arithmetic, fp32 loss and optimizer."""
+    arithmetic, fp32 loss and optimizer.  `keep` (a dict) receives the step's denoised image."""
     from sbmc_amd.utils import crop_like
     opt.zero_grad()
     with th.autocast("cuda", dtype=th.float16, enabled=fp16):
         out = model(batch)["radiance"]
     out = out.float()
+    if keep is not None:
+        keep["radiance"] = out.detach()
     tgt = crop_like(batch["target_image"], out)
     loss = loss_fn(out, tgt)
     loss.backward()
@@ -443,7 +499,7 @@ def main():
             dist.barrier()
             th.cuda.synchronize(device)
 
-    def timed(step_fn, nwarm, nsteps, store=None, events_inside=True, inside=None):
+    def timed(step_fn, nwarm, nsteps, store=None, events_inside=True, inside=None, done=None):
         """Wall time of `nsteps` steps.  `store` collects (name, start, end) HIP-event triples of the
         fused operators: inside the timed steps when `events_inside`, else in two extra, untimed
         steps: with ~50 event pairs per step switched on at the start of the 3 timed model steps they
@@ -451,7 +507,8 @@ def main():
         nor in the splat workload -- a start-up effect, not isolated further), which must not leak
         into the model workload's `value`.  `inside` = (list, name prefixes): with `events_inside` off, the operators of
         these names (the splat kernels: two event pairs per step) are timed INSIDE the timed steps all the same -- into
-        that list, warm-up steps included so that nothing switches on at the start of the timed region."""
+        that list, warm-up steps included so that nothing switches on at the start of the timed region.  `done` is called
+        once the timed steps are over and the clock is read, before any further step runs."""
         if os.environ.get("SBMC_BENCH_EVENTS_OUTSIDE"):   # debugging aid: never any event in a timed step
             events_inside = False
         if inside is not None and not events_inside:
@@ -482,6 +539,8 @@ def main():
         sync()
         dt = time.perf_counter() - t0
         functions.enable_kernel_timing(None)
+        if done is not None:
+            done()
         # per-step device time between the boundary events (no extra synchronisation): the median
         # SURVEY.md 8d asks for; `value` stays the whole-region figure the driver's contract defines
         per_step = sorted(marks[i].elapsed_time(marks[i + 1]) * 1e-3 for i in range(nsteps))
@@ -505,6 +564,16 @@ def main():
     model_timings = []
     in_step = []          # the splat operators' launches INSIDE the training step's timed region (N = 1)
     validation = None
+    stages = args.full and not args.no_stages
+    # --dump-outputs: the step functions leave what their caller receives here, step after step (references only)
+    last = {} if args.dump_outputs else None
+
+    def dump(grads=()):
+        """timed()'s `done` for the main region: the last timed step's outputs, and the gradients it left on the tensors
+        of `grads` [(name, tensors)], go to --dump-outputs (rank 0's)."""
+        if last is None or rank != 0:
+            return None
+        return lambda: dump_outputs(args.dump_outputs, dict(last, **{n: grads_of(ts) for n, ts in grads}))
 
     # ---------------------------------------------------------------- main timed region
     if is_model:
@@ -524,12 +593,16 @@ def main():
 
             def step():
                 with th.no_grad(), th.autocast("cuda", dtype=th.float16, enabled=args.fp16_activations):
-                    runner(batch)
+                    out = runner(batch)
+                if last is not None:
+                    last["radiance"] = out["radiance"]
         elif world == 1:
             batch = make_model_inputs(H, W, S, device, seed=1234)
 
             def step():
-                train_step(model, opt, loss_fn, batch, fp16=args.fp16_activations)
+                loss = train_step(model, opt, loss_fn, batch, fp16=args.fp16_activations, keep=last)
+                if last is not None:
+                    last["loss"] = loss.detach()
         else:
             batch = make_model_inputs(H, W, S, device, seed=1234, rows=(part.y0, part.y1))
             runner = sdist.ShardedDenoiser(model, part)
@@ -543,13 +616,17 @@ def main():
 
             def step():
                 try:
-                    runner.train_step(opt, loss_fn, batch)
+                    loss = runner.train_step(opt, loss_fn, batch)
                 except sdist.HaloTimeout:
                     # (raised on every rank together; the ranks have left the IPC transport: the step is repeated
                     # over torch.distributed P2P and the line says so in `transport` / `transport_note`)
-                    runner.train_step(opt, loss_fn, batch)
-        dt = timed(step, warmup, steps, timings if world == 1 else None, events_inside=False,
-                   inside=(in_step, ("splat_update_",)) if (world == 1 and not infer) else None)
+                    loss = runner.train_step(opt, loss_fn, batch)
+                if last is not None:
+                    last["loss"] = loss
+        # (--full: the per-layer figures come from two more, instrumented steps behind the timed ones)
+        dt = timed(step, warmup, steps, timings if (world == 1 and args.full) else None, events_inside=False,
+                   inside=(in_step, ("splat_update_",)) if (world == 1 and not infer) else None,
+                   done=dump([] if infer else [("grads", list(model.parameters()))]))
         med_s, spread = timed.median, timed.spread
         model_timings = timings
         if world > 1:
@@ -560,7 +637,11 @@ def main():
     elif world == 1:
         update = modules.ProgressiveKernelApply(splat=True)
         rad, logits, d_out = make_splat_inputs(H, W, S, K, device, seed=1234)
-        dt = timed(lambda: splat_step(update, rad, logits, d_out), warmup, steps, timings)
+        def step():
+            out = splat_step(update, rad, logits, d_out)
+            if last is not None:
+                last["radiance"] = out.detach()
+        dt = timed(step, warmup, steps, timings, done=dump([("d_radiance", rad), ("d_logits", logits)]))
         med_s, spread = timed.median, timed.spread
         local_px = H * W
     else:
@@ -581,14 +662,17 @@ def main():
             all_log.grad = None
             st = functions.SplatAll.apply(all_rad, all_log, *slab)
             sr, sw, _ = sdist.merge_overhang(st[0], st[1], st[2], pad, part)
-            (sr / (sw + 1e-8)).backward(d_out)
-        dt = timed(slab_step, warmup, steps, timings)
+            out = sr / (sw + 1e-8)
+            out.backward(d_out)
+            if last is not None:
+                last["radiance"] = out.detach()
+        dt = timed(slab_step, warmup, steps, timings, done=dump([("d_radiance", [all_rad]), ("d_logits", [all_log])]))
         med_s, spread = timed.median, timed.spread
         local_px = part.rows * W
 
     # ---------------------------------------------------------------- per-rank split of the sharded step
     per_rank = None
-    if is_model and world > 1:
+    if is_model and world > 1 and args.full:
         # two more, untimed, steps with events around every neighbour exchange (launches on this rank's stream:
         # they include the wait for the neighbour's rows) and around the wait for the gradient all-reduces the
         # backward did not hide; "compute" is the rest of the step
@@ -619,7 +703,7 @@ def main():
 
     # ---------------------------------------------------------------- the same step on the fp32 matrix pipe only
     fp32_pipe = None
-    if is_model and not infer and world == 1 and not args.no_stages and not args.fp16_activations:
+    if is_model and not infer and world == 1 and stages and not args.fp16_activations:
         # `value` is measured with the convolutions at fp32 ACCURACY on the f16 / bf16 matrix pipes (split precision,
         # DESIGN.md 4.6 / 4.10).  The same step with every product on the fp32 pipe (MIOpen's fp32 3x3 solvers, the
         # fp32-MFMA 1x1 kernels), same run, same box: 2 warm-up + 5 timed steps
@@ -642,7 +726,7 @@ def main():
 
     # ---------------------------------------------------------------- north_star's matrix: forward only
     infer_stages = None
-    if is_model and not infer and not args.no_stages and not args.fp16_activations:
+    if is_model and not infer and stages and not args.fp16_activations:
         # 1280x720 (this run's frame) at 4 / 8 / 32 spp, eval mode, no_grad, 5 warm-up + 10 timed frames each
         # (the timing protocol of the reference's scripts/denoise.py:152-165), on this run's ranks
         infer_stages = {}
@@ -679,7 +763,7 @@ def main():
     stage = stage_all = stage_f16 = None
     step_flops = model_flops(model, H, W, S, not infer) if is_model else None
     layout = unet_layout() if is_model else None
-    if is_model and not infer and world == 1 and not args.no_stages:
+    if is_model and not infer and world == 1 and stages:
         del model, opt
         th.cuda.empty_cache()
         if os.environ.get("SBMC_BENCH_SPLAT_COOLDOWN"):      # measurement aid: seconds of idle device before the splat stages
@@ -823,7 +907,7 @@ def main():
             "metric": "Msamples/s (SxHxW) denoise %s, %dx%d %dspp %dx%d kernel" % (
                 "fwd only" if infer else "fwd+bwd", W, H, S, K, K),
             "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world,
-            "steps": steps, "warmup": warmup, "ms_per_step": round(ms, 3),
+            "steps": steps, "warmup": warmup, "full": args.full, "ms_per_step": round(ms, 3),
             "ms_per_step_median": round(med_s * 1e3, 3),
             "ms_per_step_min_max": [round(spread[0] * 1e3, 3), round(spread[1] * 1e3, 3)],
             "value_at_median": round(S * H * W / med_s / 1e6, 2),
@@ -994,7 +1078,7 @@ def main():
                 k1 = kern["splat_update_fwd"]
                 res["roofline_fwd"]["one_sample_launches"] = {"avg_launch_ms": k1["avg_ms"], "achieved": k1["GBps"],
                                                               "frac": round(k1["GBps"] / HBM_PEAK_GBPS, 4)}
-        if world == 1 and not args.no_cpu_baseline and not infer:
+        if world == 1 and args.full and not args.no_cpu_baseline and not infer:
             try:
                 res["cpu_baseline"], parity = cpu_baseline(args, device)
                 if parity is not None:

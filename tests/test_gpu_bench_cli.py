@@ -10,8 +10,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--height", "64", "--width", "96", "--spp", "2", "--ksize", "5", "--steps", "2", "--warmup", "2",
-         "--no-cpu-baseline", "--no-stages"]
+SMALL = ["--height", "64", "--width", "96", "--spp", "2", "--ksize", "5", "--steps", "2", "--warmup", "2"]
+# what takes runs of its own sits behind --full; the CPU baseline is left out of it here, the stages where a test does not read them
+FULL = ["--full", "--no-cpu-baseline"]
 
 
 def _run(args, env=None):
@@ -25,10 +26,15 @@ def _run(args, env=None):
     return json.loads(lines[0])
 
 
+def _dumped(path):
+    import numpy as np
+    return {f.name[:-4]: np.load(str(f)) for f in sorted(path.iterdir())}
+
+
 def test_bench_line_carries_the_inference_matrix():
-    """north_star's matrix in the default line: forward-only stages at 4 / 8 / 32 spp, the forward kernel's
+    """north_star's matrix in the --full line: forward-only stages at 4 / 8 / 32 spp, the forward kernel's
     roofline entry, the whole step's TFLOP/s and the U-nets' layout (tiny frame here)."""
-    d = _run([a for a in SMALL if a != "--no-stages"])
+    d = _run(SMALL + FULL)
     for spp in (4, 8, 32):
         st = d["stages"]["infer_%dspp" % spp]
         assert st["value"] > 0 and st["unit"] == "Msamples/s" and st["steps"] == 10
@@ -36,8 +42,21 @@ def test_bench_line_carries_the_inference_matrix():
     assert "roofline" in d and "stages" in d and "splat" in d["stages"]
 
 
-def test_bench_single_gpu_line():
-    d = _run(SMALL)
+def test_bench_single_gpu_line(tmp_path):
+    """The plain line: the timed steps and nothing that takes runs of its own; --dump-outputs writes what the last timed
+    step returned."""
+    import numpy as np
+    d = _run(SMALL + ["--dump-outputs", str(tmp_path)])
+    assert d["full"] is False and d["ms_per_step"] > 0
+    for key in ("stages", "fp32_pipe", "cpu_baseline", "parity", "pointwise_layers", "conv3x3"):
+        assert key not in d, key
+    out = _dumped(tmp_path)
+    assert sorted(out) == ["grads", "loss", "radiance"]
+    for a in out.values():
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+    assert out["radiance"].ndim == 4 and out["radiance"].shape[:2] == (1, 3)
+    assert out["loss"].shape == () and out["grads"].ndim == 1
+    assert np.abs(out["grads"]).max() > 0
     assert d["n_gpus"] == 1 and d["world_size"] == 1 and d["value"] > 0 and d["unit"] == "Msamples/s"
     assert d["steps"] == 2 and d["higher_is_better"] is True and d["dtype"] == "f32"
     assert d["ms_per_step_median"] > 0 and len(d["ms_per_step_min_max"]) == 2
@@ -48,10 +67,49 @@ def test_bench_single_gpu_line():
     assert d["roofline"]["avg_launch_ms"] == ks["splat_update_bwd_all"]["avg_ms"]
 
 
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """The run is seeded and every step moves the weights, so the dump tells how many steps ran before it was taken:
+    3 timed steps behind 2 warm-up steps and 2 behind 3 (five steps either way) leave the same arrays, up to the order of
+    fp32 sums (1e-5 of an array's scale, the bound the operators are held to); 2 behind 2 leave others: Adam's early
+    updates move every weight by about the learning rate, 1e-4 against weights of 1e-2 to 1e-1, so the image and the
+    gradients follow by more than 1e-5 of their scale (the loss, a mean over the image, need only differ at all)."""
+    import numpy as np
+    runs = {}
+    for steps, warmup in ((3, 2), (2, 3), (2, 2)):
+        path = tmp_path / ("%d_%d" % (steps, warmup))
+        args = [a for a in SMALL]
+        args[args.index("--steps") + 1], args[args.index("--warmup") + 1] = str(steps), str(warmup)
+        d = _run(args + ["--dump-outputs", str(path)])
+        assert d["steps"] == steps and d["warmup"] == warmup
+        runs[steps, warmup] = _dumped(path)
+    for name, a in runs[3, 2].items():
+        scale = np.abs(a).max()
+        same = np.abs(a - runs[2, 3][name]).max() / scale
+        other = np.abs(a - runs[2, 2][name]).max() / scale
+        print(name, "five steps vs five: %.3g, five vs four: %.3g of the scale" % (same, other))
+        assert same <= 1e-5, name
+        assert other > (0 if name == "loss" else 1e-5) and other > same, name
+
+
+@pytest.mark.parametrize("workload", ["splat", "infer"])
+def test_bench_dumps_of_the_other_workloads(workload, tmp_path):
+    import numpy as np
+    names = {"splat": ["d_logits", "d_radiance", "radiance"], "infer": ["radiance"]}[workload]
+    d = _run(["--workload", workload] + SMALL + ["--dump-outputs", str(tmp_path)])
+    out = _dumped(tmp_path)
+    assert d["value"] > 0 and sorted(out) == names
+    for a in out.values():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert out["radiance"].ndim == 4 and out["radiance"].shape[:2] == (1, 3)
+
+
 @pytest.mark.parametrize("workload", ["model", "splat", "infer"])
-def test_bench_starts_its_own_ranks(workload):
-    d = _run(["--gpus", "2", "--workload", workload] + SMALL,
+def test_bench_starts_its_own_ranks(workload, tmp_path):
+    d = _run(["--gpus", "2", "--workload", workload] + SMALL + FULL + ["--no-stages", "--dump-outputs", str(tmp_path)],
              env={"SBMC_BENCH_BACKEND": "gloo", "SBMC_BENCH_SINGLE_DEVICE": "1"})
+    # rank 0's arrays; the sharded training step hands back its loss, not the image
+    assert sorted(_dumped(tmp_path)) == {"model": ["grads", "loss"], "splat": ["d_logits", "d_radiance", "radiance"],
+                                         "infer": ["radiance"]}[workload]
     assert d["n_gpus"] == 2 and d["world_size"] == 2 and d["backend"] == "gloo"
     assert d["value"] > 0 and d["scaling"] == "strong"
     assert "H-slabs x2" in d["config"]["parallelism"]

@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT
 for i in 1 2 3; do for lib in "" "$PWD/.ab/libsbmc_head.so"; do
-  SBMC_HIP_LIB=$lib timeout 400 python bench.py --fp16-activations --no-cpu-baseline --no-stages --steps 10 --warmup 3 2>/dev/null | python -c "
+  SBMC_HIP_LIB=$lib timeout 400 python bench.py --fp16-activations --full --no-cpu-baseline --no-stages --steps 10 --warmup 3 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

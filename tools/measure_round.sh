@@ -8,10 +8,10 @@ tag=${1:-r06}
 cd $GRAFT_REPO_ROOT
 o=gpurun_out/$tag
 mkdir -p $o
-( time timeout 1500 python bench.py > $o/${tag}_bench.json 2> $o/bench.err ); echo "bench rc=$?"
+( time timeout 1500 python bench.py --full > $o/${tag}_bench.json 2> $o/bench.err ); echo "bench rc=$?"
 head -c 300 $o/${tag}_bench.json; echo
 timeout 900 python bench.py --workload infer --spp 32 --fp16-activations > $o/infer32_fp16.json 2>/dev/null
-timeout 900 python bench.py --fp16-activations --no-cpu-baseline --no-stages > $o/train_fp16.json 2>/dev/null
+timeout 900 python bench.py --fp16-activations --full --no-cpu-baseline --no-stages > $o/train_fp16.json 2>/dev/null
 cat $o/infer32_fp16.json $o/train_fp16.json | grep '^{' > $o/${tag}_bench_fp16_activations.jsonl
 python - <<PY
 import json
@@ -34,7 +34,7 @@ timeout 900 python scripts/bench_ops.py > $o/${tag}_bench_ops.jsonl 2>/dev/null
   SBMC_CONV3X3_WS=0 SBMC_CONV3X3_WGRAD_W8=0 timeout 400 python tools/rank_cost.py 1 2>&1 | grep "^world" | sed "s/$/ [SBMC_CONV3X3_WS=0 SBMC_CONV3X3_WGRAD_W8=0]/"
   timeout 400 python tools/rank_cost.py 1 2>&1 | grep "^world" ) | tee $o/${tag}_rank_cost.txt
 # the real 8-rank partition as 8 communicating processes on this one GPU (gloo collectives, IPC mailboxes)
-SBMC_BENCH_BACKEND=gloo SBMC_BENCH_SINGLE_DEVICE=1 OMP_NUM_THREADS=8 timeout 1200 python bench.py --gpus 8 --steps 3 --warmup 2 --no-cpu-baseline --no-stages > $o/${tag}_bench_8ranks_one_gpu.json 2> $o/bench8.err; echo "8 ranks on one GPU rc=$?"
+SBMC_BENCH_BACKEND=gloo SBMC_BENCH_SINGLE_DEVICE=1 OMP_NUM_THREADS=8 timeout 1200 python bench.py --gpus 8 --steps 3 --warmup 2 --full --no-cpu-baseline --no-stages > $o/${tag}_bench_8ranks_one_gpu.json 2> $o/bench8.err; echo "8 ranks on one GPU rc=$?"
 head -c 400 $o/${tag}_bench_8ranks_one_gpu.json; echo
 # rocprofv3: splat + model kernel statistics, PMC passes of the splat kernels (-> <tag>_pmc.json: the bench line's traffic)
 bash tools/prof.sh $tag > $o/prof.log 2>&1; echo "prof rc=$?"
@@ -48,7 +48,7 @@ bash tools/prof_pointwise.sh > $o/prof_pw.log 2>&1; cp gpurun_out/profiles_pw/r0
 timeout 300 python tools/bench_pw_scaled.py > $o/${tag}_pointwise_launches.txt 2>&1; tail -3 $o/${tag}_pointwise_launches.txt
 # round 6: the fused 1x1 chains beside the layers they replace (+ cycles per phase), the wide forward, the pair backward
 ( SBMC_PC_TIMING=1 timeout 300 python tools/bench_pw_chain.py 2>&1 | grep -v amdgpu.ids; timeout 200 python tools/dev/bench_wide_fwd.py 2>&1 | grep SBMC; timeout 300 python tools/dev/bench_chain_bwd.py 2>&1 | grep -v amdgpu.ids ) > $o/${tag}_pointwise_chain.txt; cat $o/${tag}_pointwise_chain.txt
-SBMC_PW_CHAIN=0 SBMC_PW_WIDE_FWD=0 timeout 500 python bench.py --no-cpu-baseline --no-stages > $o/${tag}_bench_without_chains.json 2>/dev/null; head -c 200 $o/${tag}_bench_without_chains.json; echo
+SBMC_PW_CHAIN=0 SBMC_PW_WIDE_FWD=0 timeout 500 python bench.py --full --no-cpu-baseline --no-stages > $o/${tag}_bench_without_chains.json 2>/dev/null; head -c 200 $o/${tag}_bench_without_chains.json; echo
 bash tools/calibrate_fetch.sh > /dev/null 2>&1; cp gpurun_out/fetch_calibration.txt $o/${tag}_fetch_calibration.txt
 bash tools/prof_conv_stack.sh > $o/prof_conv.log 2>&1; cp gpurun_out/conv_stack/r02_conv_stack_mfma.txt $o/${tag}_conv_stack_mfma.txt; tail -3 $o/${tag}_conv_stack_mfma.txt; rm -rf gpurun_out/conv_stack
 ( timeout 300 python tools/fuzz_gpu.py --seconds 100 2>&1 | tail -2; timeout 300 python tools/fuzz_slab.py --seconds 100 2>&1 | tail -1; timeout 200 python tools/fuzz_pointwise.py --seconds 60 2>&1 | tail -1; timeout 200 python tools/fuzz_pointwise_chain.py --seconds 40 2>&1 | tail -1 ) > $o/${tag}_fuzz.txt; cat $o/${tag}_fuzz.txt | cut -c1-300

@@ -1,10 +1,11 @@
 # PMC pass over the fp16-storage splat stage (bench.py's model workload runs it as a stage): is the half strip
 # kernel memory- or VALU-bound?   gpurun -- bash tools/prof_half_splat.sh
+bench=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out/half_splat
 mkdir -p $out
-rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $out/pmc -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 2 --no-cpu-baseline > $out/pmc.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/st -o s -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 2 --no-cpu-baseline > $out/st.log 2>&1
+rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $out/pmc -o p -- python $bench --full --steps 1 --warmup 2 --no-cpu-baseline > $out/pmc.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/st -o s -- python $bench --full --steps 1 --warmup 2 --no-cpu-baseline > $out/st.log 2>&1
 python - <<'PY'
 import csv, glob, collections, os
 out = os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/half_splat"
