@@ -1755,6 +1755,11 @@ __global__ __launch_bounds__(PW_THREADS) void pw_bwd_kernel(PwBwdParams p) {
                 const int r0 = wave * 16;
                 const int nr = p.K - r0 < 16 ? (p.K - r0 > 0 ? p.K - r0 : 0) : 16;
                 const rsrc_t rgx = make_rsrc_n(gx_g + ((size_t)b * p.K + r0) * hw, (unsigned)nr * hw * SX);
+                // INVARIANT the RAW form's `vmcnt(16)` (below, before commit(nxt)) counts on: exactly 16 store instructions per
+                // wave and tile here, unconditionally (columns beyond the plane and waves beyond K store beyond the descriptor) --
+                // they are the only operations younger than the next tile's requests that the count allows for; fewer of them
+                // and the commit reads rows that have not landed.  The steady state runs against float64 in
+                // tests/test_gpu_pointwise_walk.py::test_scaled_backward_walk_vs_float64.
 #pragma unroll
                 for (int pb = 0; pb < 4; ++pb) {
                     const unsigned col = p0 + 16 * pb + (lane & 15);
@@ -2405,6 +2410,10 @@ __global__ __launch_bounds__(PW_THREADS) void pw_wide_bwd2_kernel(PwWideParams p
             // one lane offset per accumulator register (its row: rows beyond K fall outside the descriptor), the pixel
             // block as a scalar offset; columns beyond the plane through the offset's select
             const unsigned c0 = p0 + (lane & 15);
+            // INVARIANT the G2 form's `vmcnt(NX + 4 + 16)` (step's end, last chunk) counts on: exactly 16 store instructions
+            // per wave and tile here, unconditionally; with the NX x requests and the 4 gz requests issued behind the slice
+            // they are all that is younger than it.  (The default form waits with vmcnt(0); its walk, partial sums and word:
+            // tests/test_gpu_pointwise_walk.py::test_wide_backward_walk_vs_float64.  G2 is a development knob no test selects.)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned vo = ((4u * (lane >> 4) + j) * hw + c0) * 4u;

@@ -521,6 +521,15 @@ __global__ __launch_bounds__(512) void pw_chain_fwd_kernel(PwChainParams p) {
                 // it wherever it sits, 4.46 -> 4.79 ms --, an fp32 tile in LDS stored 16 bytes per lane, 4.46 <- 4.77, and 16 bytes
                 // per lane through a 4 x 4 transpose inside the lane quads (DPP; 16 pieces of 64 bytes per instruction), 4.62 -> 4.87:
                 // what a store costs is its 64-byte pieces, not the instruction.)
+                // INVARIANT wait_rows() counts on: every wave issues EXACTLY 16 store instructions here per stored layer, whatever
+                // the tile (edge tiles and waves without rows store beyond the descriptor, they do not skip).  The stores of
+                // layers 1 and 2 are YOUNGER than the request of the tile after next (issued at the top of phase 1), so
+                // nyounger may never exceed what is issued here: a store merged, dropped or made conditional makes the count
+                // too high and the next tile is read half-landed, with no error.  (More younger operations than counted --
+                // the mean's 16 stores -- only make the wait stronger.)  Every form of nyounger runs in steady state against
+                // float64 in tests/test_gpu_pointwise_walk.py::test_chain_forward_walk_vs_float64; at that size an MI355X lands
+                // the rows a tile ahead even with no wait at all, so a weak count shows only under the store traffic of
+                // test_chain_at_1280x720x4spp_equals_the_separate_layers_and_itself: change a count, run both.
                 const rsrc_t ry = rsrc_n(p.y[L] + ((size_t)b * C + r0) * hw, (unsigned)nrows * hw * 4u);
                 if (!edge) {
 #pragma unroll
@@ -557,6 +566,8 @@ __global__ __launch_bounds__(512) void pw_chain_fwd_kernel(PwChainParams p) {
                 const rsrc_t rs = rsrc_n(p.signs[L] + ((size_t)b * C + r0) * wpr, (unsigned)nrows * wpr * 4u);
                 // (row beyond the layer's width: beyond the descriptor; the tile's second word beyond the plane: switched off)
                 const unsigned off = (p0 + 32u * (lane >> 5) < hw) ? sgv : PC_OOB;
+                // (ONE store instruction per wave, unconditionally: layer 1's is the "+ 1" of wait_rows()'s nyounger -- see the
+                // invariant at the layer's stores above)
                 __builtin_amdgcn_raw_buffer_store_b32(myword, rs, off, (p0 / 32) * 4u, 0);
             }
             if constexpr (!LAST) {
@@ -871,6 +882,11 @@ __global__ __launch_bounds__(512) void pw_wide_fwd_kernel(PwWideFwdParams p) {
                     m = __builtin_fmaxf(m, (!edge || p0 + 16u * k + r < hw) ? mk : 0.f);
                 }
                 amax_run = __builtin_fmaxf(amax_run, m);
+                // INVARIANT the vmcnt(16) / vmcnt(32) at the top of the next tile count on: exactly 16 store instructions per
+                // wave and row tile here, on every tile (edge tiles and rows beyond the layer store beyond the descriptor); the
+                // stores of row tiles 2 and 3 are the only operations younger than the request of the tile after next.  The
+                // steady state runs against float64 in tests/test_gpu_pointwise_walk.py::test_wide_forward_walk_vs_float64 (and,
+                // under full store traffic, test_wide_forward_at_full_size_equals_the_row_tile_kernel).
                 if (!edge) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)

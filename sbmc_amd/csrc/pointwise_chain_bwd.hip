@@ -508,6 +508,12 @@ __global__ __launch_bounds__(512) void pw_chain_bwd_kernel(PwChainBwdParams p) {
         cb_sync();                                      // (every wave is through with gz_A and x_A)
         if (nvalid) issue_xa(nxt);
         // ---- stores, behind every request of the tile
+        // INVARIANT the wait_vm() counts of the next tile's steps rest on: these stores are the YOUNGEST operations of the tile
+        // (every request is issued before them), 16 per wave with a data gradient and the context gradient's behind them; a
+        // count taken for a request includes the stores issued since, so a store moved ahead of a request, or one more or
+        // fewer of them, makes a wait too weak and a tile is read half-landed without an error.  The steady state (with and
+        // without dx, per-pixel and per-image context) runs against float64 in
+        // tests/test_gpu_pointwise_walk.py::test_chain_pair_backward_walk_vs_float64.
         if (dx) {
             const int r0 = 16 * wave;
             const int nr = p.K0 - r0 < 16 ? (p.K0 - r0 > 0 ? p.K0 - r0 : 0) : 16;

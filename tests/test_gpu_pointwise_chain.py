@@ -51,7 +51,9 @@ CASES = [
     (3, 1, 32, (25, 40, 17), 100, 0, (2, 1, 2), False),                # narrow layers, ragged everything
     (2, 1, 64, (96, 128), 260, 1, (1, 0), False),
     (2, 2, 128, (128, 128, 128), 4, 0, (1, 2, 1), True),               # a plane of four pixels
-    (5, 1, 128, (128, 128, 128), 64 * 40, 0, (1, 1, 1), False),        # more tiles than one round of the grid at small b
+    (5, 1, 128, (128, 128, 128), 64 * 40, 0, (1, 1, 1), False),        # 200 units: a second round of the grid only below 200 CUs
+    # (a 256-CU part walks one tile per workgroup in EVERY case of this list; the multi-tile walk against float64 is
+    # tests/test_gpu_pointwise_walk.py, whose shapes follow the device's CU count)
     # (tools/fuzz_pointwise_chain.py's finds: layer 0's magnitude word carried a wave's maximum of layer 1 -- the words of
     # consecutive layers went through one shared array without a barrier between them)
     (6, 3, 113, (22, 74, 128), 1880, 0, (0, 1, 0), False),
@@ -85,8 +87,7 @@ def test_chain_forward_vs_float64(b, s, cin, couts, hw, t_mode, acts, mean, stor
         assert amaxes[l].item() == ys[l].abs().max().reshape(1).view(th.int32).item(), "magnitude word is not max |y|"
         if signs[l] is not None:
             # bit i of word j of a row = (y > 0) of pixel 32 j + i; elements within rounding of the kink may differ from float64
-            bits = ((signs[l].unsqueeze(-1) >> th.arange(32, device=dev)) & 1).reshape(b, couts[l], -1)[..., :hw].bool()
-            assert th.equal(bits, ys[l] > 0)
+            assert th.equal(_sign_bits(signs[l], hw), ys[l] > 0)
     if mean:
         m = ref[-1].view(b // s, s, couts[-1], hw).mean(1)
         assert (ymean.double() - m).abs().max().item() <= 1e-5 * m.abs().max().item()
@@ -265,6 +266,31 @@ def _word(t):
     return t.abs().max().reshape(1).view(th.int32).clone()
 
 
+def _sign_bits(signs, hw):
+    """sign words [b, c, ceil(hw / 32)] -> bool [b, c, hw]: bit i of word j of a row = (y > 0) of pixel 32 j + i"""
+    b, c, _ = signs.shape
+    return ((signs.unsqueeze(-1) >> th.arange(32, device=signs.device)) & 1).reshape(b, c, -1)[..., :hw].bool()
+
+
+def _pack_signs(bits):
+    """bool [b, c, hw] -> the sign words a forward would have stored (int32 [b, c, ceil(hw / 32)], zero beyond the plane)"""
+    b, c, hw = bits.shape
+    wpr = (hw + 31) // 32
+    pad = th.zeros(b, c, wpr * 32, dtype=th.bool, device=bits.device)
+    pad[..., :hw] = bits
+    words = (pad.view(b, c, wpr, 32).long() << th.arange(32, device=bits.device)).sum(-1)
+    return th.where(words >= 2 ** 31, words - 2 ** 32, words).to(th.int32).contiguous()
+
+
+def _pair_gz64(gy, pos1, pos0, w1, act1, sl1, act0, sl0):
+    """float64 pre-activation gradients of two consecutive layers taking the forward's own decisions (pos1, pos0: its stored
+    outputs > 0) -> gz1 [b, c1, hw], gz0 [b, c0, hw]"""
+    gz1 = gy.double() * (th.where(pos1, 1.0, 0.0 if act1 == 1 else sl1) if act1 else 1.0)
+    gy0 = th.einsum("ok,bop->bkp", w1.double(), gz1)
+    gz0 = gy0 * (th.where(pos0, 1.0, 0.0 if act0 == 1 else sl0) if act0 else 1.0)
+    return gz1, gz0
+
+
 @pytest.mark.parametrize("loose", [1.0, 23.0])
 @pytest.mark.parametrize("b,s,cin,hw,t_mode,act1,act0,dx", [
     (4, 2, 128, 64 * 5 + 12, 2, 2, 2, True),      # the regressor's first two layers: per-pixel context gradient
@@ -287,12 +313,8 @@ def test_chain_pair_backward_vs_float64(b, s, cin, hw, t_mode, act1, act0, dx, l
     y = _chain64(x, t, s, layers)
     y0 = y[0].float()                                   # what the forward stored (its decisions: y0 > 0)
     y1 = y[1].float()
-    wpr = (hw + 31) // 32
     bits = (y1 > 0)
-    pad = th.zeros(b, 128, wpr * 32, dtype=th.bool, device=dev)
-    pad[..., :hw] = bits
-    signs1 = (pad.view(b, 128, wpr, 32).long() << th.arange(32, device=dev)).sum(-1)
-    signs1 = th.where(signs1 >= 2 ** 31, signs1 - 2 ** 32, signs1).to(th.int32).contiguous()
+    signs1 = _pack_signs(bits)
     th.manual_seed(3)
     gy = th.randn(b, 128, hw, device=dev) * 1e-2
     gy[:, :, ::5] *= 20.0
@@ -310,9 +332,7 @@ def test_chain_pair_backward_vs_float64(b, s, cin, hw, t_mode, act1, act0, dx, l
         _lib.ptr(gt) if gt is not None else None, _lib.ptr(words[0]), _lib.ptr(words[1]), _lib.ptr(words[2]),
         _lib.ptr(gxmax) if dx else None, b, s, cin, hw, t_mode, act1, sl1, act0, sl0, _lib.current_stream(dev)), "chain_bwd")
     # float64 with the same decisions
-    gz1 = gy.double() * (th.where(bits, 1.0, 0.0 if act1 == 1 else sl1) if act1 else 1.0)
-    gy0 = th.einsum("ok,bop->bkp", w1.double(), gz1)
-    gz0 = gy0 * (th.where(y0 > 0, 1.0, 0.0 if act0 == 1 else sl0) if act0 else 1.0)
+    gz1, gz0 = _pair_gz64(gy, bits, y0 > 0, w1, act1, sl1, act0, sl0)
     y0d, xd = y0.double(), x.double()
     close_sum(gwp1.sum(0), th.einsum("bop,bkp->ok", gz1, y0d), th.einsum("bop,bkp->ok", gz1.abs(), y0d.abs()), what="gw1")
     close_sum(gbp1.sum(0), gz1.sum((0, 2)), gz1.abs().sum((0, 2)), what="gb1")

@@ -108,6 +108,29 @@ def test_scaled_forward_with_a_loose_word_and_zeros():
         assert (y.double() - want).abs().max().item() <= 1e-5 * want.abs().max().item()
 
 
+def _backward64(x, w, pos, gy, gmean, s, t_mode, act, slope):
+    """float64 backward of one layer taking the SAME activation decisions as the forward (pos: y > 0 as it stored them)
+    -> gx, gw, gbias, gt (per image [b / s, cout], per pixel [b / s, cout, hw], or None); gmean: the gradient of the mean
+    over groups of s images, or None."""
+    b, cout, hw = gy.shape
+    gtot = gy.double()
+    if gmean is not None:
+        gtot = gtot + (gmean.double() / s).repeat_interleave(s, 0)
+    if act == 0:
+        gz = gtot
+    else:
+        gz = th.where(pos, gtot, gtot * (slope if act == 2 else 0.0))
+    gx64 = th.matmul(w.double().t(), gz)
+    gw64 = th.einsum("bop,bkp->ok", gz, x.double())
+    gb64 = gz.sum((0, 2))
+    gt64 = None
+    if t_mode == 1:
+        gt64 = gz.view(b // s, s, cout, hw).sum((1, 3))
+    elif t_mode == 2:
+        gt64 = gz.view(b // s, s, cout, hw).sum(1)
+    return gx64, gw64, gb64, gt64
+
+
 BWD_CASES = [
     # b, s, cin, cout, hw, t_mode, act, gm, dx
     (2, 1, 128, 128, 1024, 0, 2, False, True),
@@ -145,22 +168,7 @@ def test_scaled_backward_vs_float64(b, s, cin, cout, hw, t_mode, act, gm, dx, sp
     _lib.check(L.sbmc_pointwise_fwd_scaled_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(t) if t is not None else None,
                                                _lib.ptr(y), _lib.ptr(signs), None, 1, _lib.ptr(_word(x)), None, b, s, cin, cout,
                                                hw, t_mode, act, slope, _lib.current_stream(dev)), "fwd")
-    # float64 of the same layer with the SAME activation decisions (y > 0 as the forward stored them)
-    gtot = gy.double()
-    if gm:
-        gtot = gtot + (gmean.double() / s).repeat_interleave(s, 0)
-    if act == 0:
-        gz = gtot
-    else:
-        gz = th.where(y > 0, gtot, gtot * (slope if act == 2 else 0.0))
-    gx64 = th.matmul(w.double().t(), gz)
-    gw64 = th.einsum("bop,bkp->ok", gz, x.double())
-    gb64 = gz.sum((0, 2))
-    gt64 = None
-    if t_mode == 1:
-        gt64 = gz.view(b // s, s, cout, hw).sum((1, 3))
-    elif t_mode == 2:
-        gt64 = gz.view(b // s, s, cout, hw).sum(1)
+    gx64, gw64, gb64, gt64 = _backward64(x, w, y > 0, gy, gmean, s, t_mode, act, slope)
     for scaled in (True, False):
         groups = L.sbmc_pointwise_bwd_groups(b, s, 1 if (gm and t_mode == 0) else t_mode, hw)    # (as functions.py)
         nb = b // s if t_mode == 1 else 1

@@ -1,6 +1,9 @@
 """Randomised sweep of the fused 1x1 chains (csrc/pointwise_chain.hip) against float64: random layer counts, widths, plane sizes
 (ragged tiles), context forms, activations, magnitudes; the wide forward and the pair backward with them.
-    python tools/fuzz_pointwise_chain.py [--seconds N] [--seed S]"""
+    python tools/fuzz_pointwise_chain.py [--seconds N] [--seed S] [--walk]
+--walk: shapes from tests/test_gpu_pointwise_walk.py's walk_shape -- 3 to 6 units per workgroup on THIS device's CU count, ragged
+planes, tensors capped at about 100 MB -- so that the time goes to the kernels' steady state (the default draw, b <= 12 and
+hw <= 2800, rarely leaves a 256-CU part's workgroups more than one tile each).  The default draw is unchanged."""
 import os
 import sys
 import time
@@ -12,24 +15,43 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from sbmc_amd import _lib, functions as funcs  # noqa: E402
 from test_gpu_pointwise_chain import _chain64  # noqa: E402
+from test_gpu_pointwise_walk import walk_shape  # noqa: E402
 
 dev = th.device("cuda")
 L = _lib.lib()
 seconds = float(sys.argv[sys.argv.index("--seconds") + 1]) if "--seconds" in sys.argv else 60.0
 seed = int(sys.argv[sys.argv.index("--seed") + 1]) if "--seed" in sys.argv else 0
+walk = "--walk" in sys.argv
+cus = th.cuda.get_device_properties(0).multi_processor_count
 g = th.Generator().manual_seed(seed)
 ri = lambda lo, hi: int(th.randint(lo, hi + 1, (1,), generator=g))
 worst = {"chain": 0.0, "wide": 0.0}
 n = {"chain": 0, "wide": 0}
 t0 = time.time()
 while time.time() - t0 < seconds:
-    s = ri(1, 4)
-    b = s * ri(1, 3)
-    hw = 4 * ri(1, 700)
+    if walk:
+        # units (planes x tiles of a plane) between 3 x and 6 x the grid, the plane's last tile of 4 .. 60 pixels; the widest
+        # tensor (b x 512 or 128 channels x hw floats) stays at about 100 MB: few planes of many tiles where s > 1
+        s = ri(1, 4)
+        planes, hw = walk_shape(cus, planes=ri(2, 24), rounds=3.0 + 3.0 * ri(0, 1000) / 1000.0)
+        hw += 4 * ri(1, 15) - 20
+        b = s * planes
+        while s > 1 and b * hw * 128 * 4 > 100e6:
+            s -= 1
+            b = s * planes
+    else:
+        s = ri(1, 4)
+        b = s * ri(1, 3)
+        hw = 4 * ri(1, 700)
     spread = 10.0 ** ri(-4, 2)
     th.manual_seed(ri(0, 10 ** 6))
     if ri(0, 3) == 0:
         cin, cout, act = ri(1, 128), ri(129, 512), ri(0, 2)
+        if walk:
+            b = planes                                  # (the wide forward walks images, not groups of s)
+            cout = min(cout, int(100e6 / (b * hw * 4)))
+            if cout <= 128:
+                continue
         x = th.randn(b, cin, hw, device=dev) * spread
         w = th.randn(cout, cin, device=dev) / cin ** 0.5 / spread
         bias = th.randn(cout, device=dev)
