@@ -41,7 +41,7 @@ extern "C" {
 #define SBMC_API
 #endif
 
-#define SBMC_HIP_ABI_VERSION 8
+#define SBMC_HIP_ABI_VERSION 9
 #define SBMC_HIP_EINVAL (-1)
 /* largest channel count the fused/plain kernels take in one call */
 #define SBMC_HIP_MAX_CHANNELS 8
@@ -792,6 +792,39 @@ SBMC_API int sbmc_conv3x3_wgrad_bias_f32(const float *gy, const unsigned *gmax, 
                                 float *gw, long s_co, long s_ci, long s_ky, long s_kx, void *scratch, int n, int h,
                                 int w, int cin, int cout, const float *bias_partial, int bias_chunks, int bias_c,
                                 float *gbias, void *stream);
+
+
+/*
+ * ABI 9 -- 5 x 5 convolution, stride 1, dilation 1, NO padding ("valid"), of a channels-last fp32 image -- replaces
+ * `torch.nn.Conv2d(..., 5)` in the reference's ConvChain as KPCN builds it (reference sbmc/models.py:221-291: two chains
+ * of nine such layers, 27 -> 100 (x 8) -> k^2 channels) at fp32 accuracy on the f16 matrix pipe (csrc/conv5x5.hip: the
+ * arithmetic of sbmc_conv3x3_*, two f16 planes per operand, three products per term, power-of-two scales from the
+ * tensors' largest magnitudes taken on the device).  Inference only: there is no gradient kernel.
+ *   Any channel count >= 1: the tensors live in channels-last buffers [n][h][w][ld] whose CHANNEL STRIDE ld is a
+ *   multiple of 16 and >= the channel count (padded_channels(c): the smallest such stride); the channels from c up to
+ *   ld of an input must hold exact zeros, and the kernel writes exact zeros there in its output.
+ *   supported:        n, cin, cout >= 1, h >= 5, w >= 5 and sizes whose byte offsets inside a tile fit 31 bits
+ *   weights_bytes:    size of the prepared weights of one layer (0: unsupported)
+ *   padded_channels:  the channel stride of a buffer of c channels (0 for c < 1)
+ *   prepare_weights:  w[co][ci][ky][kx] with element strides s_* (storage_elems floats of dense storage, 16-byte
+ *                     aligned) -> wp: the two f16 planes in the kernel's stage order, zero-padded, + scale and magnitude
+ *   bias_act_nhwc:    y[n][h - 4][w - 4][co] = act(bias[co] + sum x[n][h + ky][w + kx][ci] w[co][ci][ky][kx]),
+ *                     act(v) = v > 0 ? v : slope v  (slope 1: linear, 0: ReLU, else LeakyReLU); xmax: the bit pattern
+ *                     of (a bound of) max |x| (sbmc_conv3x3_absmax_f32, or the amax word of the layer before);
+ *                     amax (or NULL): raised to the bit pattern of max |y| (a word the caller zeroed).
+ *                     x, wp, y 16-byte aligned; SBMC_HIP_EINVAL otherwise, for h < 5, w < 5 and unsupported sizes.
+ *   pack / unpack:    planar x[n][c][hw] -> channels-last y[n][hw][ldy] (zeros from c up) and back
+ */
+SBMC_API int sbmc_conv5x5_supported(int n, int h, int w, int cin, int cout);
+SBMC_API size_t sbmc_conv5x5_weights_bytes(int cin, int cout);
+SBMC_API int sbmc_conv5x5_padded_channels(int c);
+SBMC_API int sbmc_conv5x5_prepare_weights_f32(const float *w, long s_co, long s_ci, long s_ky, long s_kx,
+                                     long storage_elems, int cin, int cout, void *wp, void *stream);
+SBMC_API int sbmc_conv5x5_bias_act_nhwc_f32(const float *x, int ldx, const unsigned *xmax, const void *wp,
+                                   const float *bias, float *y, int ldy, int n, int h, int w, int cin, int cout,
+                                   float slope, unsigned *amax, void *stream);
+SBMC_API int sbmc_conv5x5_pack_nchw_f32(const float *x, float *y, int ldy, int n, int c, long hw, void *stream);
+SBMC_API int sbmc_conv5x5_unpack_nhwc_f32(const float *x, int ldx, float *y, int n, int c, long hw, void *stream);
 
 
 /*

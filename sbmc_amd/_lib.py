@@ -133,10 +133,17 @@ SYMBOLS = (
     "sbmc_conv3x3_bias_act_nhwc_f16",
     "sbmc_conv3x3_wgrad_bias_f16",
     "sbmc_bias_act_nhwc_bwd_signs_f16",
+    "sbmc_conv5x5_supported",
+    "sbmc_conv5x5_weights_bytes",
+    "sbmc_conv5x5_padded_channels",
+    "sbmc_conv5x5_prepare_weights_f32",
+    "sbmc_conv5x5_bias_act_nhwc_f32",
+    "sbmc_conv5x5_pack_nchw_f32",
+    "sbmc_conv5x5_unpack_nhwc_f32",
     "sbmc_wbank_forward_f32",
     "sbmc_wbank_backward_f32",
 )
-ABI_VERSION = 8
+ABI_VERSION = 9
 WBANK_MAX = 24
 
 
@@ -318,11 +325,19 @@ def lib():
     handle.sbmc_conv3x3_bias_act_nhwc_f16.argtypes = [p, p, p, p, p, i, i, i, i, i, i, ctypes.c_float, p, p]
     handle.sbmc_conv3x3_wgrad_bias_f16.argtypes = [p, p, p, lg, lg, lg, lg, p, i, i, i, i, i, p, i, i, p, p]
     handle.sbmc_bias_act_nhwc_bwd_signs_f16.argtypes = [p, p, p, p, lg, i, i, ctypes.c_float, p]
+    handle.sbmc_conv5x5_supported.argtypes = [i] * 5
+    handle.sbmc_conv5x5_weights_bytes.argtypes = [i, i]
+    handle.sbmc_conv5x5_padded_channels.argtypes = [i]
+    handle.sbmc_conv5x5_prepare_weights_f32.argtypes = [p, lg, lg, lg, lg, lg, i, i, p, p]
+    handle.sbmc_conv5x5_bias_act_nhwc_f32.argtypes = [p, i, p, p, p, p, i, i, i, i, i, i, ctypes.c_float, p, p]
+    handle.sbmc_conv5x5_pack_nchw_f32.argtypes = [p, p, i, i, i, lg, p]
+    handle.sbmc_conv5x5_unpack_nhwc_f32.argtypes = [p, i, p, i, i, lg, p]
     for name in SYMBOLS[2:]:
         getattr(handle, name).restype = i
     handle.sbmc_halo_bytes.restype = ctypes.c_size_t
     handle.sbmc_pointwise_wide_bwd_ws_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_weights_bytes.restype = ctypes.c_size_t
+    handle.sbmc_conv5x5_weights_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_workspace_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_wgrad_scratch_bytes.restype = ctypes.c_size_t
     handle.sbmc_splat_update_bwd_scratch_bytes.restype = ctypes.c_size_t

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libsbmc_hip.so")
-SOURCES = ["plain_ops.hip", "splat_fused.hip", "bias_act.hip", "pointwise.hip", "pointwise_chain.hip", "pointwise_chain_bwd.hip", "resample.hip", "nhwc_ops.hip", "halo.hip", "conv3x3.hip"]
+SOURCES = ["plain_ops.hip", "splat_fused.hip", "bias_act.hip", "pointwise.hip", "pointwise_chain.hip", "pointwise_chain_bwd.hip", "resample.hip", "nhwc_ops.hip", "halo.hip", "conv3x3.hip", "conv5x5.hip"]
 ARCH = "gfx950"
 
 
@@ -31,7 +31,7 @@ STAMP = LIB + ".srchash"
 def _source_hash():
     """Hash of everything the library is built from (sources, headers, flags)."""
     import hashlib
-    h = hashlib.sha256((ARCH + " -O3 -std=c++17").encode())
+    h = hashlib.sha256((ARCH + " -O3 -std=c++17" + "".join(" %s: %s" % (k, " ".join(v)) for k, v in sorted(EXTRA_FLAGS.items()))).encode())
     for path in [os.path.join(CSRC, src) for src in SOURCES] + _headers():
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
@@ -54,6 +54,8 @@ def is_stale():
 
 OBJ_DIR = os.path.join(HERE, ".obj")
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
+#: per source, on top of FLAGS.  conv5x5.hip: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in generated code
+EXTRA_FLAGS = {"conv5x5.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 _COMPILER_ID = None
@@ -79,7 +81,7 @@ def _headers():
 def _object_hash(src):
     """Hash of what ONE object file is built from: its source, every header of csrc/, the flags, the compiler."""
     import hashlib
-    h = hashlib.sha256((" ".join(FLAGS) + "\0" + _compiler_id()).encode())
+    h = hashlib.sha256((" ".join(FLAGS + EXTRA_FLAGS.get(src, [])) + "\0" + _compiler_id()).encode())
     for path in [os.path.join(CSRC, src)] + _headers():
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
@@ -114,7 +116,7 @@ def _compile(src, verbose):
     tmp = "%s.%d.tmp" % (obj, os.getpid())
     # (the compiler's per-kernel resource remarks -- registers, spills, scratch, occupancy -- are kept next to the object:
     # tools/kernel_resources.py and tests/test_kernel_resources.py read them instead of compiling the file once more)
-    cmd = [_hipcc()] + FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", tmp, os.path.join(CSRC, src)]
+    cmd = [_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", tmp, os.path.join(CSRC, src)]
     if verbose:
         print(" ".join(cmd), flush=True)
     try:
@@ -123,7 +125,9 @@ def _compile(src, verbose):
         if res.returncode != 0:
             sys.stderr.write(err)
             raise subprocess.CalledProcessError(res.returncode, cmd)
-        other = [ln for ln in err.splitlines() if "remark:" not in ln and "[-Rpass-analysis" not in ln]
+        # (EXTRA_FLAGS' target feature is the device's: the host pass of the same command says it does not know it)
+        other = [ln for ln in err.splitlines() if "remark:" not in ln and "[-Rpass-analysis" not in ln
+                 and "is not a recognized feature for this target" not in ln]
         if any(ln.strip() for ln in other):
             sys.stderr.write("\n".join(other) + "\n")                  # (warnings: always shown)
         with open(tmp + ".remarks", "w") as f:

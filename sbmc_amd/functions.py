@@ -1855,6 +1855,75 @@ class UpsampleCatNHWC(th.autograd.Function):
         return gcoarse, gleft, None, None, None
 
 
+def conv5x5_chain_supported(x, channels):
+    """Can `conv5x5_chain` run a chain of unpadded 5 x 5 convolutions with the channel counts `channels` = [cin, c1, ...,
+    cout] on x [b, cin, h, w]?  (fp32 on a GPU, SBMC_CONV5X5 not 0, every layer's shape one csrc/conv5x5.hip takes.)"""
+    if not (x.is_cuda and x.dtype == th.float32 and x.dim() == 4 and x.numel() > 0 and x.shape[1] == channels[0]):
+        return False
+    if knob("SBMC_CONV5X5") == 0:
+        return False
+    L = _lib.lib()
+    b, _, h, w = (int(v) for v in x.shape)
+    for cin, cout in zip(channels[:-1], channels[1:]):
+        if not L.sbmc_conv5x5_supported(b, h, w, int(cin), int(cout)):
+            return False
+        h, w = h - 4, w - 4
+    return True
+
+
+def conv5x5_chain(x, layers):
+    """A chain of 5 x 5, stride-1, unpadded convolutions with bias and activation -- KPCN's ConvChains (reference
+    sbmc/models.py:221-291: `torch.nn.Conv2d(..., 5)` + ReLU, nine deep) -- on csrc/conv5x5.hip: fp32 accuracy from three
+    f16 matrix products per term.  INFERENCE only: the result carries no autograd graph.
+
+    x [b, cin, h, w] planar fp32; layers: [(weight [cout, cin, 5, 5], bias [cout], act, slope), ...] with act 0 linear /
+    1 ReLU / 2 LeakyReLU(slope) -> [b, cout, h - 4 L, w - 4 L] planar contiguous.
+
+    x is packed once into a channels-last buffer whose channel stride is rounded up to what the kernel wants (zeros in
+    the padding channels; the kernel keeps them zero from layer to layer), the weights are prepared per call (~1 MB a
+    layer), each layer's epilogue leaves the magnitude word the next one scales by (no absmax pass, no host
+    synchronisation), and the last layer's output is unpacked to planar."""
+    _require_f32("conv5x5_chain", x=x)
+    L = _lib.lib()
+    dev = x.device
+    x = x.detach().contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    b, c, h, w = (int(v) for v in x.shape)
+    with th.cuda.device(dev), th.no_grad(), _timed("conv5x5_chain %dx%dx%dx%d" % (b, c, h, w), dev):
+        stream = _lib.current_stream(dev)
+        ld = L.sbmc_conv5x5_padded_channels(c)
+        buf = th.empty((b, h, w, ld), dtype=th.float32, device=dev)
+        _lib.check(L.sbmc_conv5x5_pack_nchw_f32(_lib.ptr(x), _lib.ptr(buf), ld, b, c, h * w, stream), "conv5x5_pack")
+        xmax = Conv3x3NHWC._absmax(x)                       # (the same values: the padding is zeros)
+        words = th.zeros(max(len(layers), 1), dtype=th.int32, device=dev)
+        for i, (weight, bias, act, slope) in enumerate(layers):
+            _require_f32("conv5x5_chain", weight=weight, bias=bias)
+            cout = int(weight.shape[0])
+            if tuple(weight.shape[1:]) != (c, 5, 5) or tuple(bias.shape) != (cout,) or act not in (0, 1, 2):
+                raise ValueError("conv5x5_chain: layer %d takes %s, the chain has %d channels there" % (i, tuple(weight.shape), c))
+            if not L.sbmc_conv5x5_supported(b, h, w, c, cout):
+                raise ValueError("conv5x5_chain: layer %d (%d -> %d channels on %d x %d) is not supported" % (i, c, cout, h, w))
+            wt = weight.detach()
+            if wt.data_ptr() % 16 or not wt.is_contiguous():
+                wt = wt.contiguous().clone()
+            s = wt.stride()
+            wp = th.empty(L.sbmc_conv5x5_weights_bytes(c, cout), dtype=th.uint8, device=dev)
+            _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[0], s[1], s[2], s[3], wt.numel(), c, cout,
+                                                          _lib.ptr(wp), stream), "conv5x5_prepare_weights")
+            ldy = L.sbmc_conv5x5_padded_channels(cout)
+            y = th.empty((b, h - 4, w - 4, ldy), dtype=th.float32, device=dev)
+            amax = words[i:i + 1] if i + 1 < len(layers) else None
+            _lib.check(L.sbmc_conv5x5_bias_act_nhwc_f32(
+                _lib.ptr(buf), ld, _lib.ptr(xmax), _lib.ptr(wp), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), ldy,
+                b, h, w, c, cout, 1.0 if act == 0 else (0.0 if act == 1 else float(slope)), _lib.ptr(amax), stream),
+                "conv5x5_bias_act_nhwc")
+            buf, ld, xmax, c, h, w = y, ldy, amax, cout, h - 4, w - 4
+        out = th.empty((b, c, h, w), dtype=th.float32, device=dev)
+        _lib.check(L.sbmc_conv5x5_unpack_nhwc_f32(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, stream), "conv5x5_unpack")
+    return out
+
+
 def gather_update_supported(data, kernels):
     """True when the fused gather-kernel update (`SplatUpdate(..., gather=True)`) applies."""
     if not (data.is_cuda and kernels.is_cuda) or data.dtype != th.float32 or kernels.dtype != th.float32:

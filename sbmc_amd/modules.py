@@ -448,6 +448,48 @@ class ConvChain(nn.Module):
             return y + conv.bias.view(1, -1, 1, 1), False
         return funcs.BiasAct.apply(y, conv.bias, act, slope), act != 0
 
+    @staticmethod
+    def _conv5x5_plan(mods, x):
+        """The layers of a chain that csrc/conv5x5.hip runs as a whole (functions.conv5x5_chain): every convolution 5 x 5,
+        stride 1, unpadded, with a bias; ReLU / LeakyReLU between them and linear / ReLU / LeakyReLU at the end; no
+        normalisation; fp32 without autocast; and NO GRADIENT wanted -- the kernel has no backward, so with grad mode on and
+        anything that requires grad the chain runs as before (MIOpen).  KPCN's two chains at inference (reference
+        sbmc/models.py:221-291).  -> [(weight, bias, act, slope), ...] or None."""
+        first = mods[0].layer[0] if (mods and isinstance(mods[0], ConvChain._ConvBNRelu)) else (mods[0] if mods else None)
+        if not isinstance(first, nn.Conv2d) or first.kernel_size != (5, 5):
+            return None
+        if x.dtype != th.float32 or x.dim() != 4 or th.is_autocast_enabled():
+            return None
+        plan, i = [], 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, ConvChain._ConvBNRelu) and len(m.layer) == 2:
+                conv, act_mod, i = m.layer[0], m.layer[1], i + 1
+            elif isinstance(m, nn.Conv2d):
+                conv, act_mod = m, (mods[i + 1] if i + 1 < len(mods) else None)
+                i += 1 if act_mod is None else 2
+            else:
+                return None
+            if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (5, 5) and conv.stride == (1, 1)
+                    and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None):
+                return None
+            if act_mod is None:
+                act = (0, 0.0)
+            elif isinstance(act_mod, nn.ReLU):
+                act = (1, 0.0)
+            elif isinstance(act_mod, nn.LeakyReLU):
+                act = (2, float(act_mod.negative_slope))
+            else:
+                return None
+            plan.append((conv, act))
+        if i != len(mods) or [c.in_channels for c, _ in plan[1:]] != [c.out_channels for c, _ in plan[:-1]]:
+            return None
+        if th.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for c, _ in plan for p in c.parameters())):
+            return None
+        if not funcs.conv5x5_chain_supported(x, [plan[0][0].in_channels] + [c.out_channels for c, _ in plan]):
+            return None
+        return [(conv_weight(c), c.bias, a[0], a[1]) for c, a in plan]
+
     def _run(self, mods, x, mean_s=0, mean_out=None, halo=None, want_link=False):
         """halo: the chain runs on a row slab of a frame sharded over several GPUs (sbmc_amd.dist) -- a tuple
         (pad, crop[, refresh]): before every padded k x k convolution `pad(x, k // 2)` attaches the neighbouring
@@ -455,6 +497,10 @@ class ConvChain(nn.Module):
         padding beyond them (lazily: just before the next exchange, or at the end, so that in-place activations
         never meet a view).  `refresh(y, k // 2)`, where given and applicable (it returns None otherwise), does
         crop + pad without copying the slab: the stale outer rows of `y` are overwritten by the neighbours'."""
+        if halo is None and not mean_s and not want_link and x.is_cuda:
+            plan = ConvChain._conv5x5_plan(mods, x)
+            if plan is not None:
+                return funcs.conv5x5_chain(x, plan)
         gemm = self.pointwise_as_gemm and x.is_cuda
         pending = 0                                                # halo rows still to be dropped
         i = 0

@@ -36,8 +36,11 @@ def timeit(fn, reps, warm=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--only", default="", help="kpcn: only KPCN's 5 x 5 convolutions")
     args = ap.parse_args()
     dev = th.device("cuda")
+    if args.only == "kpcn":
+        return kpcn_convs(dev, args.reps)
     shapes = [("profile-script shape (bs4,c3,128x128,k21)", 4, 3, 128, 128, 21),
               ("720p (bs1,c3,1280x720,k21)", 1, 3, 720, 1280, 21)]
     for label, bs, c, h, w, k in shapes:
@@ -89,6 +92,7 @@ def main():
         del data, wts, go, gs, out, sw, dd, dw, s2g, kern, kg, dg, st, gst
         th.cuda.empty_cache()
     cnn_glue(dev, args.reps)
+    kpcn_convs(dev, args.reps)
 
 
 def cnn_glue(dev, reps):
@@ -141,6 +145,92 @@ def cnn_glue(dev, reps):
     emit("upsample x2 + concat bwd (gather adjoint)",
          lambda: th.autograd.grad(out, [coarse], g, retain_graph=True),
          nbytes=4.0 * (4 * coarse.numel() + coarse.numel()))
+
+
+F16_PEAK = 2500.0      # TFLOP/s, dense f16 MFMA
+
+
+def kpcn_convs(dev, reps):
+    """KPCN's nine 5 x 5 valid convolutions at 1280x720 (27 -> 100 (x 8) -> 441, the frame 4 pixels smaller per layer):
+    csrc/conv5x5.hip (bias + ReLU in its epilogue) against the library convolution + bias + ReLU it replaces, ALTERNATING
+    in one process -- median and range over the repetitions -- and the whole KPCN(27) forward under no_grad with
+    SBMC_CONV5X5 = 0 / 1.  f16 rate: the three f16 products per term the kernel issues on its padded shape (16 on the
+    reduction side, 128 on the output side, whole 16 x 16 tiles) against the dense f16 peak."""
+    import torch.nn.functional as nnf
+    from sbmc_amd import KPCN, _lib
+    L = _lib.lib()
+    reps = max(3, min(reps, 10))
+
+    def stats(ts):
+        ts = sorted(ts)
+        return dict(ms=round(ts[len(ts) // 2], 4), ms_min=round(ts[0], 4), ms_max=round(ts[-1], 4))
+
+    def alternate(fns):
+        """[name -> fn] timed in turn, `reps` rounds after one warm-up round -> {name: [ms]}"""
+        out = {k: [] for k in fns}
+        for r in range(reps + 1):
+            for k, fn in fns.items():
+                a, b = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                th.cuda.synchronize()
+                if r:
+                    out[k].append(a.elapsed_time(b))
+        return out
+
+    H, W = 720, 1280
+    stream = _lib.current_stream(dev)
+    for i, (cin, cout) in enumerate([(27, 100)] + [(100, 100)] * 7 + [(100, 441)]):
+        h, w = H - 4 * i, W - 4 * i
+        x = th.randn(1, cin, h, w, device=dev)
+        wt = th.randn(cout, cin, 5, 5, device=dev) * (2.0 / (25 * cin)) ** 0.5
+        bias = th.randn(cout, device=dev) * 0.1
+        ldx, ldy = L.sbmc_conv5x5_padded_channels(cin), L.sbmc_conv5x5_padded_channels(cout)
+        xb = th.empty(1, h, w, ldx, device=dev)
+        _lib.check(L.sbmc_conv5x5_pack_nchw_f32(_lib.ptr(x), _lib.ptr(xb), ldx, 1, cin, h * w, stream), "pack")
+        xmax = F.Conv3x3NHWC._absmax(x)
+        wp = th.empty(L.sbmc_conv5x5_weights_bytes(cin, cout), dtype=th.uint8, device=dev)
+        s = wt.stride()
+        _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[0], s[1], s[2], s[3], wt.numel(), cin, cout,
+                                                      _lib.ptr(wp), stream), "prepare")
+        yb = th.empty(1, h - 4, w - 4, ldy, device=dev)
+        amax = th.zeros(1, dtype=th.int32, device=dev)
+        ours = lambda: _lib.check(L.sbmc_conv5x5_bias_act_nhwc_f32(
+            _lib.ptr(xb), ldx, _lib.ptr(xmax), _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(yb), ldy, 1, h, w, cin, cout, 0.0,
+            _lib.ptr(amax), stream), "conv5x5")
+        res = alternate({"conv5x5.hip": ours, "library": lambda: nnf.relu_(nnf.conv2d(x, wt, bias))})
+        px = (h - 4) * (w - 4)
+        issued = 6.0 * 25 * ldx * (-(-cout // 128) * 128) * (-(-(h - 4) // 16) * 16) * (-(-(w - 4) // 16) * 16)
+        for k, ts in res.items():
+            rec = {"op": "KPCN layer %d: 5x5 valid %d->%d + bias + ReLU, %s" % (i, cin, cout, k), "shape": "%dx%d" % (w, h)}
+            rec.update(stats(ts))
+            rec["true_TFLOPs"] = round(2.0 * 25 * cin * cout * px / (rec["ms"] * 1e-3) / 1e12, 1)
+            if k == "conv5x5.hip":
+                rec["f16_product_TFLOPs"] = round(issued / (rec["ms"] * 1e-3) / 1e12, 1)
+                rec["frac_of_f16_peak"] = round(issued / (rec["ms"] * 1e-3) / 1e12 / F16_PEAK, 4)
+            print(json.dumps(rec))
+        del x, xb, yb, wp
+        th.cuda.empty_cache()
+    model = KPCN(27).to(dev)
+    data = {k: th.randn(1, 27, H, W, device=dev) for k in ("kpcn_diffuse_in", "kpcn_specular_in")}
+    data.update({k: th.rand(1, 3, H, W, device=dev) for k in ("kpcn_diffuse_buffer", "kpcn_specular_buffer", "kpcn_albedo")})
+
+    def forward(flag):
+        def run():
+            os.environ["SBMC_CONV5X5"] = flag
+            with th.no_grad():
+                model(data)
+        return run
+    before = os.environ.get("SBMC_CONV5X5")
+    res = alternate({"SBMC_CONV5X5=1": forward("1"), "SBMC_CONV5X5=0": forward("0")})
+    os.environ.pop("SBMC_CONV5X5")
+    if before is not None:
+        os.environ["SBMC_CONV5X5"] = before
+    for k, ts in res.items():
+        rec = {"op": "KPCN(27) forward, no_grad, %s" % k, "shape": "%dx%d" % (W, H)}
+        rec.update(stats(ts))
+        print(json.dumps(rec))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,32 @@
+"""csrc/conv5x5.hip without a GPU: the host arithmetic of its C ABI, and what the compiler made of the kernel."""
+import os
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_shapes_strides_and_sizes():
+    from sbmc_amd import _lib
+    L = _lib.lib()
+    assert [L.sbmc_conv5x5_padded_channels(c) for c in (0, 1, 16, 27, 100, 441)] == [0, 16, 16, 32, 112, 448]
+    assert L.sbmc_conv5x5_supported(1, 720, 1280, 27, 100) == 1 and L.sbmc_conv5x5_supported(1, 5, 5, 1, 1) == 1
+    assert L.sbmc_conv5x5_supported(1, 4, 720, 27, 100) == 0 and L.sbmc_conv5x5_supported(1, 720, 4, 27, 100) == 0
+    # K rounded up to 16, N to the 128-channel tile; a stage = 5 taps x 2 planes x 2 octets x 128 entries of 16 bytes
+    assert L.sbmc_conv5x5_weights_bytes(100, 441) == 4 * 7 * 5 * 2560 * 16 + 16
+    assert L.sbmc_conv5x5_weights_bytes(100, 0) == 0
+    assert L.sbmc_conv5x5_bias_act_nhwc_f32(None, 32, None, None, None, None, 112, 1, 9, 9, 27, 100, 0.0, None, None) == -1
+
+
+@pytest.mark.slow
+def test_conv5_kernel_does_not_spill():
+    """One wave per SIMD on the whole register file, 256 of it accumulators: a spill goes to scratch inside the MFMA stream."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    rows = kernel_resources.resources(os.path.join(ROOT, "sbmc_amd", "csrc", "conv5x5.hip"))
+    main = [r for r in rows if "conv5_kernel" in r["name"]]
+    assert len(main) == 1 and len(rows) == 4, rows
+    for r in rows:
+        assert r["scratch"] == 0 and r["spill"] == 0, r
+    assert main[0]["occupancy"] == 1, main
