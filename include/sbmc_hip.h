@@ -41,7 +41,7 @@ extern "C" {
 #define SBMC_API
 #endif
 
-#define SBMC_HIP_ABI_VERSION 9
+#define SBMC_HIP_ABI_VERSION 10
 #define SBMC_HIP_EINVAL (-1)
 /* largest channel count the fused/plain kernels take in one call */
 #define SBMC_HIP_MAX_CHANNELS 8
@@ -799,7 +799,7 @@ SBMC_API int sbmc_conv3x3_wgrad_bias_f32(const float *gy, const unsigned *gmax, 
  * `torch.nn.Conv2d(..., 5)` in the reference's ConvChain as KPCN builds it (reference sbmc/models.py:221-291: two chains
  * of nine such layers, 27 -> 100 (x 8) -> k^2 channels) at fp32 accuracy on the f16 matrix pipe (csrc/conv5x5.hip: the
  * arithmetic of sbmc_conv3x3_*, two f16 planes per operand, three products per term, power-of-two scales from the
- * tensors' largest magnitudes taken on the device).  Inference only: there is no gradient kernel.
+ * tensors' largest magnitudes taken on the device).  The gradients: ABI 10 below.
  *   Any channel count >= 1: the tensors live in channels-last buffers [n][h][w][ld] whose CHANNEL STRIDE ld is a
  *   multiple of 16 and >= the channel count (padded_channels(c): the smallest such stride); the channels from c up to
  *   ld of an input must hold exact zeros, and the kernel writes exact zeros there in its output.
@@ -825,6 +825,39 @@ SBMC_API int sbmc_conv5x5_bias_act_nhwc_f32(const float *x, int ldx, const unsig
                                    float slope, unsigned *amax, void *stream);
 SBMC_API int sbmc_conv5x5_pack_nchw_f32(const float *x, float *y, int ldy, int n, int c, long hw, void *stream);
 SBMC_API int sbmc_conv5x5_unpack_nhwc_f32(const float *x, int ldx, float *y, int n, int c, long hw, void *stream);
+
+/*
+ * ABI 10 -- the gradients of that convolution -- replace `torch.nn.Conv2d`'s backward in the reference's ConvChain as KPCN
+ * trains it (reference sbmc/models.py:221-291) -- on the same channels-last buffers (channel strides ldg / ldx multiples
+ * of 16, exact zeros in the padding channels, kept in what is written), scales and arithmetic (csrc/conv5x5_grad.hip).
+ * h, w are the layer's INPUT size everywhere; gz [n][h - 4][w - 4][ldg] is the gradient of the layer's pre-activation.
+ *   dgrad_supported / wgrad_supported:  n, cin, cout >= 1, h, w >= 5 and sizes whose byte offsets inside a tile's rows
+ *                     (dgrad) / inside one row (wgrad) fit 31 bits
+ *   dgrad_adj_nhwc:   gx[n][y][x][ci] = act'(xsaved[n][y][x][ci]) sum gz[n][y - ky][x - kx][co] w[co][ci][ky][kx],
+ *                     act'(v) = v > 0 ? 1 : slope: the adjoint of the activation of the layer that PRODUCED this layer's
+ *                     input, read from that input (xsaved [n][h][w][ldx]; NULL: none to undo).  wp_swapped: the weights
+ *                     prepared by sbmc_conv5x5_prepare_weights_f32(w, s_ci, s_co, s_ky, s_kx, elems, cout, cin, ...) --
+ *                     the two channel strides and counts exchanged; the kernel mirrors the taps.  gmax: bit pattern of (a
+ *                     bound of) max |gz|; amax (or NULL): raised to the bit pattern of max |gx| (a word the caller zeroed).
+ *   act_adjoint_nhwc: g[i] *= act'(ysaved[i]) over elems floats (a multiple of 16) and amax raised to max |g|: the adjoint of
+ *                     a chain's last activation, in front of the first wgrad / dgrad.
+ *   wgrad_bias:       gw[co][ci][ky][kx] (element strides s_*) = sum gz[n][y][x][co] x[n][y + ky][x + kx][ci], gb[co] = sum gz;
+ *                     gmax / xmax: the tensors' magnitude words; scratch: wgrad_scratch_bytes of device memory (partial sums
+ *                     of the pixel ranges, added in a fixed order: the result does not depend on the run).
+ * SBMC_HIP_EINVAL for null or misaligned pointers (16 bytes for tensors, prepared weights and scratch), channel strides
+ * that are no multiple of 16 or smaller than the count, h < 5, w < 5 and offsets beyond 31 bits.
+ */
+SBMC_API int sbmc_conv5x5_dgrad_supported(int n, int h, int w, int cin, int cout);
+SBMC_API int sbmc_conv5x5_dgrad_adj_nhwc_f32(const float *gz, int ldg, const unsigned *gmax, const void *wp_swapped,
+                                    const float *xsaved, float slope, float *gx, int ldx, int n, int h, int w, int cin,
+                                    int cout, unsigned *amax, void *stream);
+SBMC_API int sbmc_conv5x5_act_adjoint_nhwc_f32(float *g, const float *ysaved, float slope, long elems, unsigned *amax,
+                                      void *stream);
+SBMC_API int sbmc_conv5x5_wgrad_supported(int n, int h, int w, int cin, int cout);
+SBMC_API size_t sbmc_conv5x5_wgrad_scratch_bytes(int n, int h, int w, int cin, int cout);
+SBMC_API int sbmc_conv5x5_wgrad_bias_f32(const float *gz, int ldg, const unsigned *gmax, const float *x, int ldx,
+                                const unsigned *xmax, float *gw, long s_co, long s_ci, long s_ky, long s_kx, float *gb,
+                                void *scratch, int n, int h, int w, int cin, int cout, void *stream);
 
 
 /*

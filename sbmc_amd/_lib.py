@@ -140,10 +140,16 @@ SYMBOLS = (
     "sbmc_conv5x5_bias_act_nhwc_f32",
     "sbmc_conv5x5_pack_nchw_f32",
     "sbmc_conv5x5_unpack_nhwc_f32",
+    "sbmc_conv5x5_dgrad_supported",
+    "sbmc_conv5x5_dgrad_adj_nhwc_f32",
+    "sbmc_conv5x5_act_adjoint_nhwc_f32",
+    "sbmc_conv5x5_wgrad_supported",
+    "sbmc_conv5x5_wgrad_scratch_bytes",
+    "sbmc_conv5x5_wgrad_bias_f32",
     "sbmc_wbank_forward_f32",
     "sbmc_wbank_backward_f32",
 )
-ABI_VERSION = 9
+ABI_VERSION = 10
 WBANK_MAX = 24
 
 
@@ -332,12 +338,19 @@ def lib():
     handle.sbmc_conv5x5_bias_act_nhwc_f32.argtypes = [p, i, p, p, p, p, i, i, i, i, i, i, ctypes.c_float, p, p]
     handle.sbmc_conv5x5_pack_nchw_f32.argtypes = [p, p, i, i, i, lg, p]
     handle.sbmc_conv5x5_unpack_nhwc_f32.argtypes = [p, i, p, i, i, lg, p]
+    handle.sbmc_conv5x5_dgrad_supported.argtypes = [i] * 5
+    handle.sbmc_conv5x5_dgrad_adj_nhwc_f32.argtypes = [p, i, p, p, p, ctypes.c_float, p, i, i, i, i, i, i, p, p]
+    handle.sbmc_conv5x5_act_adjoint_nhwc_f32.argtypes = [p, p, ctypes.c_float, lg, p, p]
+    handle.sbmc_conv5x5_wgrad_supported.argtypes = [i] * 5
+    handle.sbmc_conv5x5_wgrad_scratch_bytes.argtypes = [i] * 5
+    handle.sbmc_conv5x5_wgrad_bias_f32.argtypes = [p, i, p, p, i, p, p, lg, lg, lg, lg, p, p, i, i, i, i, i, p]
     for name in SYMBOLS[2:]:
         getattr(handle, name).restype = i
     handle.sbmc_halo_bytes.restype = ctypes.c_size_t
     handle.sbmc_pointwise_wide_bwd_ws_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_weights_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv5x5_weights_bytes.restype = ctypes.c_size_t
+    handle.sbmc_conv5x5_wgrad_scratch_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_workspace_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_wgrad_scratch_bytes.restype = ctypes.c_size_t
     handle.sbmc_splat_update_bwd_scratch_bytes.restype = ctypes.c_size_t

@@ -1874,7 +1874,7 @@ def conv5x5_chain_supported(x, channels):
 def conv5x5_chain(x, layers):
     """A chain of 5 x 5, stride-1, unpadded convolutions with bias and activation -- KPCN's ConvChains (reference
     sbmc/models.py:221-291: `torch.nn.Conv2d(..., 5)` + ReLU, nine deep) -- on csrc/conv5x5.hip: fp32 accuracy from three
-    f16 matrix products per term.  INFERENCE only: the result carries no autograd graph.
+    f16 matrix products per term.  INFERENCE only: the result carries no autograd graph (training: `Conv5x5ChainTrain`).
 
     x [b, cin, h, w] planar fp32; layers: [(weight [cout, cin, 5, 5], bias [cout], act, slope), ...] with act 0 linear /
     1 ReLU / 2 LeakyReLU(slope) -> [b, cout, h - 4 L, w - 4 L] planar contiguous.
@@ -1922,6 +1922,156 @@ def conv5x5_chain(x, layers):
         out = th.empty((b, c, h, w), dtype=th.float32, device=dev)
         _lib.check(L.sbmc_conv5x5_unpack_nhwc_f32(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, stream), "conv5x5_unpack")
     return out
+
+
+def conv5x5_chain_train_supported(x, channels):
+    """Can `Conv5x5ChainTrain` run the chain `conv5x5_chain_supported` accepts WITH its gradients?  (SBMC_CONV5X5_TRAIN = 1
+    -- the default 0 keeps training on the library --, and csrc/conv5x5_grad.hip takes every layer's shape.)"""
+    if knob("SBMC_CONV5X5_TRAIN", 0) != 1 or not conv5x5_chain_supported(x, channels):
+        return False
+    L = _lib.lib()
+    b, _, h, w = (int(v) for v in x.shape)
+    for cin, cout in zip(channels[:-1], channels[1:]):
+        if not (L.sbmc_conv5x5_dgrad_supported(b, h, w, int(cin), int(cout))
+                and L.sbmc_conv5x5_wgrad_supported(b, h, w, int(cin), int(cout))):
+            return False
+        h, w = h - 4, w - 4
+    return True
+
+
+class Conv5x5ChainTrain(th.autograd.Function):
+    """`conv5x5_chain` with a backward: KPCN's ConvChains in training (reference sbmc/models.py:221-291, `torch.nn.Conv2d`'s
+    forward and backward) on csrc/conv5x5.hip and csrc/conv5x5_grad.hip -- no library convolution and no host
+    synchronisation in either direction.
+
+    apply(x, acts, w0, b0, w1, b1, ...): x [b, cin, h, w] planar fp32; acts: ((act, slope), ...) per layer, act 0 linear /
+    1 ReLU / 2 LeakyReLU(slope >= 0: the adjoint reads the sign off the ACTIVATED value) -> [b, cout, h - 4 L, w - 4 L].
+
+    Forward: the inference loop, keeping every layer's channels-last input and its magnitude word (and the last layer's
+    output where it is activated).  Backward: the gradient packed to channels-last (the last activation's adjoint applied
+    there), then per layer from the last one weight + bias gradient in one launch and, where something below wants a
+    gradient, the data gradient with the activation adjoint of the layer below in its epilogue, which also leaves the
+    magnitude word the next launches scale by.  The first layer's data gradient runs only if x requires grad."""
+
+    @staticmethod
+    def _slope(act, slope):
+        return 1.0 if act == 0 else (0.0 if act == 1 else float(slope))
+
+    @staticmethod
+    def forward(ctx, x, acts, *params):
+        _require_f32("Conv5x5ChainTrain", x=x)
+        L = _lib.lib()
+        dev = x.device
+        x = x.detach().contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()
+        b, c, h, w = (int(v) for v in x.shape)
+        nl = len(acts)
+        if len(params) != 2 * nl or nl < 1:
+            raise ValueError("Conv5x5ChainTrain: %d layers, %d parameters" % (nl, len(params)))
+        saved = []                                   # per layer: (input buffer, ld, magnitude word, c, h, w)
+        with th.cuda.device(dev), _timed("conv5x5_chain_train %dx%dx%dx%d" % (b, c, h, w), dev):
+            stream = _lib.current_stream(dev)
+            ld = L.sbmc_conv5x5_padded_channels(c)
+            buf = th.empty((b, h, w, ld), dtype=th.float32, device=dev)
+            _lib.check(L.sbmc_conv5x5_pack_nchw_f32(_lib.ptr(x), _lib.ptr(buf), ld, b, c, h * w, stream), "conv5x5_pack")
+            xmax = Conv3x3NHWC._absmax(x)
+            words = th.zeros(nl, dtype=th.int32, device=dev)
+            for i in range(nl):
+                weight, bias = params[2 * i], params[2 * i + 1]
+                act, slope = acts[i]
+                _require_f32("Conv5x5ChainTrain", weight=weight, bias=bias)
+                cout = int(weight.shape[0])
+                if tuple(weight.shape[1:]) != (c, 5, 5) or tuple(bias.shape) != (cout,) or act not in (0, 1, 2) or (act == 2 and slope < 0):
+                    raise ValueError("Conv5x5ChainTrain: layer %d takes %s, the chain has %d channels there" % (i, tuple(weight.shape), c))
+                if not (L.sbmc_conv5x5_supported(b, h, w, c, cout) and L.sbmc_conv5x5_dgrad_supported(b, h, w, c, cout)
+                        and L.sbmc_conv5x5_wgrad_supported(b, h, w, c, cout)):
+                    raise ValueError("Conv5x5ChainTrain: layer %d (%d -> %d channels on %d x %d) is not supported" % (i, c, cout, h, w))
+                wt = weight.detach()
+                if wt.data_ptr() % 16 or not wt.is_contiguous():
+                    wt = wt.contiguous().clone()
+                s = wt.stride()
+                wp = th.empty(L.sbmc_conv5x5_weights_bytes(c, cout), dtype=th.uint8, device=dev)
+                _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[0], s[1], s[2], s[3], wt.numel(), c, cout,
+                                                              _lib.ptr(wp), stream), "conv5x5_prepare_weights")
+                ldy = L.sbmc_conv5x5_padded_channels(cout)
+                y = th.empty((b, h - 4, w - 4, ldy), dtype=th.float32, device=dev)
+                amax = words[i:i + 1]
+                _lib.check(L.sbmc_conv5x5_bias_act_nhwc_f32(
+                    _lib.ptr(buf), ld, _lib.ptr(xmax), _lib.ptr(wp), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), ldy,
+                    b, h, w, c, cout, Conv5x5ChainTrain._slope(act, slope), _lib.ptr(amax), stream), "conv5x5_bias_act_nhwc")
+                saved.append((buf, ld, xmax, c, h, w))
+                buf, ld, xmax, c, h, w = y, ldy, amax, cout, h - 4, w - 4
+            out = th.empty((b, c, h, w), dtype=th.float32, device=dev)
+            _lib.check(L.sbmc_conv5x5_unpack_nhwc_f32(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, stream), "conv5x5_unpack")
+        ctx.acts, ctx.saved, ctx.batch = tuple(acts), saved, b
+        ctx.last = (buf if acts[-1][0] != 0 else None, ld, c, h, w)
+        ctx.save_for_backward(*params)
+        return out
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, g):
+        L = _lib.lib()
+        params, acts, saved, b = ctx.saved_tensors, ctx.acts, ctx.saved, ctx.batch
+        ylast, ldg, cout, ho, wo = ctx.last
+        dev = g.device
+        _require_f32("Conv5x5ChainTrain.backward", g=g)
+        g = g.contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        nl = len(acts)
+        grads = [None] * (2 * nl)
+        gx = None
+        with th.cuda.device(dev), _timed("conv5x5_chain_train_bwd %dx%dx%dx%d" % (b, cout, ho, wo), dev):
+            stream = _lib.current_stream(dev)
+            gz = th.empty((b, ho, wo, ldg), dtype=th.float32, device=dev)
+            _lib.check(L.sbmc_conv5x5_pack_nchw_f32(_lib.ptr(g), _lib.ptr(gz), ldg, b, cout, ho * wo, stream), "conv5x5_pack")
+            words = th.zeros(nl + 1, dtype=th.int32, device=dev)
+            if ylast is not None:
+                gmax = words[nl:nl + 1]
+                _lib.check(L.sbmc_conv5x5_act_adjoint_nhwc_f32(_lib.ptr(gz), _lib.ptr(ylast), Conv5x5ChainTrain._slope(*acts[-1]),
+                                                               gz.numel(), _lib.ptr(gmax), stream), "conv5x5_act_adjoint")
+            else:
+                gmax = Conv3x3NHWC._absmax(g)
+            for i in range(nl - 1, -1, -1):
+                xin, ldx, xmax, cin, h, w = saved[i]
+                weight = params[2 * i]
+                need_w = ctx.needs_input_grad[2 + 2 * i] or ctx.needs_input_grad[3 + 2 * i]
+                need_x = ctx.needs_input_grad[0] or any(ctx.needs_input_grad[2:2 + 2 * i])
+                if need_w:
+                    gw = th.empty(weight.shape, dtype=th.float32, device=dev)
+                    gb = th.empty(cout, dtype=th.float32, device=dev)
+                    scratch = th.empty(L.sbmc_conv5x5_wgrad_scratch_bytes(b, h, w, cin, cout), dtype=th.uint8, device=dev)
+                    s = gw.stride()
+                    _lib.check(L.sbmc_conv5x5_wgrad_bias_f32(
+                        _lib.ptr(gz), ldg, _lib.ptr(gmax), _lib.ptr(xin), ldx, _lib.ptr(xmax), _lib.ptr(gw), s[0], s[1], s[2], s[3],
+                        _lib.ptr(gb), _lib.ptr(scratch), b, h, w, cin, cout, stream), "conv5x5_wgrad_bias")
+                    grads[2 * i], grads[2 * i + 1] = gw, gb
+                if not need_x:
+                    break
+                # the weights with the channel sides exchanged, once per backward and layer; the kernel mirrors the taps
+                wt = weight.detach()
+                if wt.data_ptr() % 16 or not wt.is_contiguous():
+                    wt = wt.contiguous().clone()
+                s = wt.stride()
+                wp = th.empty(L.sbmc_conv5x5_weights_bytes(cout, cin), dtype=th.uint8, device=dev)
+                _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[1], s[0], s[2], s[3], wt.numel(), cout, cin,
+                                                              _lib.ptr(wp), stream), "conv5x5_prepare_weights")
+                below = acts[i - 1] if i > 0 else (0, 1.0)
+                undo = xin if below[0] != 0 else None
+                gnext = th.empty((b, h, w, ldx), dtype=th.float32, device=dev)
+                amax = words[i:i + 1]
+                _lib.check(L.sbmc_conv5x5_dgrad_adj_nhwc_f32(
+                    _lib.ptr(gz), ldg, _lib.ptr(gmax), _lib.ptr(wp), _lib.ptr(undo), Conv5x5ChainTrain._slope(*below),
+                    _lib.ptr(gnext), ldx, b, h, w, cin, cout, _lib.ptr(amax), stream), "conv5x5_dgrad_adj")
+                gz, ldg, gmax, cout, ho, wo = gnext, ldx, amax, cin, h, w
+            else:
+                if ctx.needs_input_grad[0]:
+                    gx = th.empty((b, cout, ho, wo), dtype=th.float32, device=dev)
+                    _lib.check(L.sbmc_conv5x5_unpack_nhwc_f32(_lib.ptr(gz), ldg, _lib.ptr(gx), b, cout, ho * wo, stream), "conv5x5_unpack")
+        grads = [gr if ctx.needs_input_grad[2 + k] else None for k, gr in enumerate(grads)]
+        return (gx, None) + tuple(grads)
 
 
 def gather_update_supported(data, kernels):

@@ -452,9 +452,9 @@ class ConvChain(nn.Module):
     def _conv5x5_plan(mods, x):
         """The layers of a chain that csrc/conv5x5.hip runs as a whole (functions.conv5x5_chain): every convolution 5 x 5,
         stride 1, unpadded, with a bias; ReLU / LeakyReLU between them and linear / ReLU / LeakyReLU at the end; no
-        normalisation; fp32 without autocast; and NO GRADIENT wanted -- the kernel has no backward, so with grad mode on and
-        anything that requires grad the chain runs as before (MIOpen).  KPCN's two chains at inference (reference
-        sbmc/models.py:221-291).  -> [(weight, bias, act, slope), ...] or None."""
+        normalisation; fp32 without autocast.  With grad mode on and anything that requires grad the chain runs as before
+        (MIOpen) unless SBMC_CONV5X5_TRAIN = 1 and csrc/conv5x5_grad.hip takes every layer (functions.Conv5x5ChainTrain).
+        KPCN's two chains (reference sbmc/models.py:221-291).  -> [(weight, bias, act, slope), ...] or None."""
         first = mods[0].layer[0] if (mods and isinstance(mods[0], ConvChain._ConvBNRelu)) else (mods[0] if mods else None)
         if not isinstance(first, nn.Conv2d) or first.kernel_size != (5, 5):
             return None
@@ -484,11 +484,22 @@ class ConvChain(nn.Module):
             plan.append((conv, act))
         if i != len(mods) or [c.in_channels for c, _ in plan[1:]] != [c.out_channels for c, _ in plan[:-1]]:
             return None
-        if th.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for c, _ in plan for p in c.parameters())):
-            return None
-        if not funcs.conv5x5_chain_supported(x, [plan[0][0].in_channels] + [c.out_channels for c, _ in plan]):
+        channels = [plan[0][0].in_channels] + [c.out_channels for c, _ in plan]
+        if ConvChain._conv5x5_wants_grad(x, plan):
+            # training: only with SBMC_CONV5X5_TRAIN = 1 (default 0: the library, as before), gradient kernels for every
+            # layer, and slopes >= 0 -- the activation adjoint reads the sign off the ACTIVATED value
+            if any(a[1] < 0 for _, a in plan) or not funcs.conv5x5_chain_train_supported(x, channels):
+                return None
+        elif not funcs.conv5x5_chain_supported(x, channels):
             return None
         return [(conv_weight(c), c.bias, a[0], a[1]) for c, a in plan]
+
+    @staticmethod
+    def _conv5x5_wants_grad(x, plan):
+        """plan: [(conv, (act, slope)), ...] -- does autograd want anything from this chain?"""
+        if not th.is_grad_enabled():
+            return False
+        return x.requires_grad or any(p.requires_grad for c, _ in plan for p in c.parameters())
 
     def _run(self, mods, x, mean_s=0, mean_out=None, halo=None, want_link=False):
         """halo: the chain runs on a row slab of a frame sharded over several GPUs (sbmc_amd.dist) -- a tuple
@@ -500,6 +511,9 @@ class ConvChain(nn.Module):
         if halo is None and not mean_s and not want_link and x.is_cuda:
             plan = ConvChain._conv5x5_plan(mods, x)
             if plan is not None:
+                if th.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for wt, b, _, _ in plan for t in (wt, b))):
+                    return funcs.Conv5x5ChainTrain.apply(x, tuple((a, s) for _, _, a, s in plan),
+                                                         *[t for wt, b, _, _ in plan for t in (wt, b)])
                 return funcs.conv5x5_chain(x, plan)
         gemm = self.pointwise_as_gemm and x.is_cuda
         pending = 0                                                # halo rows still to be dropped

@@ -154,7 +154,8 @@ def kpcn_convs(dev, reps):
     """KPCN's nine 5 x 5 valid convolutions at 1280x720 (27 -> 100 (x 8) -> 441, the frame 4 pixels smaller per layer):
     csrc/conv5x5.hip (bias + ReLU in its epilogue) against the library convolution + bias + ReLU it replaces, ALTERNATING
     in one process -- median and range over the repetitions -- and the whole KPCN(27) forward under no_grad with
-    SBMC_CONV5X5 = 0 / 1.  f16 rate: the three f16 products per term the kernel issues on its padded shape (16 on the
+    SBMC_CONV5X5 = 0 / 1; per layer also the data and the weight (+ bias) gradient of csrc/conv5x5_grad.hip against
+    torch.autograd.grad of F.conv2d, and the whole forward + backward with SBMC_CONV5X5_TRAIN = 0 / 1.  f16 rate: the three f16 products per term the kernel issues on its padded shape (16 on the
     reduction side, 128 on the output side, whole 16 x 16 tiles) against the dense f16 peak."""
     import torch.nn.functional as nnf
     from sbmc_amd import KPCN, _lib
@@ -210,7 +211,33 @@ def kpcn_convs(dev, reps):
                 rec["f16_product_TFLOPs"] = round(issued / (rec["ms"] * 1e-3) / 1e12, 1)
                 rec["frac_of_f16_peak"] = round(issued / (rec["ms"] * 1e-3) / 1e12 / F16_PEAK, 4)
             print(json.dumps(rec))
-        del x, xb, yb, wp
+        # the gradients (csrc/conv5x5_grad.hip) against the library's: torch.autograd.grad of F.conv2d on the same tensors
+        gz = th.randn(1, cout, h - 4, w - 4, device=dev)
+        gzb = th.empty(1, h - 4, w - 4, ldy, device=dev)
+        _lib.check(L.sbmc_conv5x5_pack_nchw_f32(_lib.ptr(gz), _lib.ptr(gzb), ldy, 1, cout, px, stream), "pack")
+        gmax = F.Conv3x3NHWC._absmax(gz)
+        wps = th.empty(L.sbmc_conv5x5_weights_bytes(cout, cin), dtype=th.uint8, device=dev)
+        _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[1], s[0], s[2], s[3], wt.numel(), cout, cin,
+                                                      _lib.ptr(wps), stream), "prepare")
+        gxb, gw, gb = th.empty_like(xb), th.empty_like(wt), th.empty_like(bias)
+        scratch = th.empty(L.sbmc_conv5x5_wgrad_scratch_bytes(1, h, w, cin, cout), dtype=th.uint8, device=dev)
+        xr, wr = x.clone().requires_grad_(), wt.clone().requires_grad_()
+        yl = nnf.conv2d(xr, wr)
+        res = alternate({
+            "dgrad, conv5x5_grad.hip": lambda: _lib.check(L.sbmc_conv5x5_dgrad_adj_nhwc_f32(
+                _lib.ptr(gzb), ldy, _lib.ptr(gmax), _lib.ptr(wps), _lib.ptr(xb), 0.0, _lib.ptr(gxb), ldx, 1, h, w, cin, cout,
+                _lib.ptr(amax), stream), "dgrad"),
+            "dgrad, library": lambda: th.autograd.grad(yl, xr, gz, retain_graph=True),
+            "wgrad + bias, conv5x5_grad.hip": lambda: _lib.check(L.sbmc_conv5x5_wgrad_bias_f32(
+                _lib.ptr(gzb), ldy, _lib.ptr(gmax), _lib.ptr(xb), ldx, _lib.ptr(xmax), _lib.ptr(gw), s[0], s[1], s[2], s[3],
+                _lib.ptr(gb), _lib.ptr(scratch), 1, h, w, cin, cout, stream), "wgrad"),
+            "wgrad, library": lambda: th.autograd.grad(yl, wr, gz, retain_graph=True)})
+        for k, ts in res.items():
+            rec = {"op": "KPCN layer %d: 5x5 valid %d->%d %s" % (i, cin, cout, k), "shape": "%dx%d" % (w, h)}
+            rec.update(stats(ts))
+            rec["true_TFLOPs"] = round(2.0 * 25 * cin * cout * px / (rec["ms"] * 1e-3) / 1e12, 1)
+            print(json.dumps(rec))
+        del x, xb, yb, wp, gz, gzb, wps, gxb, scratch, xr, wr, yl
         th.cuda.empty_cache()
     model = KPCN(27).to(dev)
     data = {k: th.randn(1, 27, H, W, device=dev) for k in ("kpcn_diffuse_in", "kpcn_specular_in")}
@@ -229,6 +256,22 @@ def kpcn_convs(dev, reps):
         os.environ["SBMC_CONV5X5"] = before
     for k, ts in res.items():
         rec = {"op": "KPCN(27) forward, no_grad, %s" % k, "shape": "%dx%d" % (W, H)}
+        rec.update(stats(ts))
+        print(json.dumps(rec))
+
+    def train(flag):
+        def run():
+            os.environ["SBMC_CONV5X5_TRAIN"] = flag
+            model.zero_grad(set_to_none=True)
+            model(data)["radiance"].sum().backward()
+        return run
+    before = os.environ.get("SBMC_CONV5X5_TRAIN")
+    res = alternate({"SBMC_CONV5X5_TRAIN=1": train("1"), "SBMC_CONV5X5_TRAIN=0": train("0")})
+    os.environ.pop("SBMC_CONV5X5_TRAIN")
+    if before is not None:
+        os.environ["SBMC_CONV5X5_TRAIN"] = before
+    for k, ts in res.items():
+        rec = {"op": "KPCN(27) forward + radiance.sum().backward(), %s" % k, "shape": "%dx%d" % (W, H)}
         rec.update(stats(ts))
         print(json.dumps(rec))
 
