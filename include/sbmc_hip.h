@@ -41,7 +41,7 @@ extern "C" {
 #define SBMC_API
 #endif
 
-#define SBMC_HIP_ABI_VERSION 10
+#define SBMC_HIP_ABI_VERSION 11
 #define SBMC_HIP_EINVAL (-1)
 /* largest channel count the fused/plain kernels take in one call */
 #define SBMC_HIP_MAX_CHANNELS 8
@@ -858,6 +858,35 @@ SBMC_API size_t sbmc_conv5x5_wgrad_scratch_bytes(int n, int h, int w, int cin, i
 SBMC_API int sbmc_conv5x5_wgrad_bias_f32(const float *gz, int ldg, const unsigned *gmax, const float *x, int ldx,
                                 const unsigned *xmax, float *gw, long s_co, long s_ci, long s_ky, long s_kx, float *gb,
                                 void *scratch, int n, int h, int w, int cin, int cout, void *stream);
+
+
+/*
+ * ABI 11 -- the same 5 x 5 valid convolution on HALF activations -- replaces `torch.nn.Conv2d(..., 5)` of the reference's
+ * ConvChain as KPCN builds it (reference sbmc/models.py:221-291) under torch.autocast(float16), where the library's half
+ * solvers ran it (csrc/conv5x5_half.hip).  Autocast's arithmetic: the half inputs as they are, the fp32 weights rounded
+ * to half once at preparation, exact products summed in fp32 on the f16 matrix pipe, bias and activation in fp32, one
+ * rounding to half on the store; no scales and no magnitude words.  Channels-last buffers of _Float16 with the channel
+ * strides of sbmc_conv5x5_padded_channels, exact zeros in the padding channels, kept in what is written.
+ *   half_supported:       n, cin, cout >= 1, h >= 5, w >= 5 and sizes whose byte offsets inside a tile fit 31 bits
+ *   half_weights_bytes:   size of the prepared weights of one layer (0: unsupported)
+ *   half_prepare_weights: fp32 w[co][ci][ky][kx] with element strides s_* -> wp: halves in the kernel's stage order,
+ *                         zero-padded (wp 16-byte aligned)
+ *   half_bias_act_nhwc:   y[n][h - 4][w - 4][co] = half(act(bias[co] + sum x[n][h + ky][w + kx][ci] half(w[co][ci][ky][kx]))),
+ *                         act(v) = v > 0 ? v : slope v; x, y: _Float16, 16-byte aligned; bias: fp32
+ *   half_pack_nchw_f32 / _f16: planar fp32 / half x[n][c][hw] -> channels-last half y[n][hw][ldy] (round to nearest,
+ *                         zeros from c up); half_unpack_nhwc: channels-last half -> planar half
+ * SBMC_HIP_EINVAL for null or misaligned pointers, channel strides that are no multiple of 16 or smaller than the count,
+ * h < 5, w < 5 and offsets beyond 31 bits; nothing is launched then.
+ */
+SBMC_API int sbmc_conv5x5_half_supported(int n, int h, int w, int cin, int cout);
+SBMC_API size_t sbmc_conv5x5_half_weights_bytes(int cin, int cout);
+SBMC_API int sbmc_conv5x5_half_prepare_weights(const float *w, long s_co, long s_ci, long s_ky, long s_kx, int cin, int cout,
+                                      void *wp, void *stream);
+SBMC_API int sbmc_conv5x5_half_pack_nchw_f32(const float *x, void *y, int ldy, int n, int c, long hw, void *stream);
+SBMC_API int sbmc_conv5x5_half_pack_nchw_f16(const void *x, void *y, int ldy, int n, int c, long hw, void *stream);
+SBMC_API int sbmc_conv5x5_half_unpack_nhwc(const void *x, int ldx, void *y, int n, int c, long hw, void *stream);
+SBMC_API int sbmc_conv5x5_half_bias_act_nhwc(const void *x, int ldx, const void *wp, const float *bias, void *y, int ldy,
+                                    int n, int h, int w, int cin, int cout, float slope, void *stream);
 
 
 /*

@@ -146,10 +146,17 @@ SYMBOLS = (
     "sbmc_conv5x5_wgrad_supported",
     "sbmc_conv5x5_wgrad_scratch_bytes",
     "sbmc_conv5x5_wgrad_bias_f32",
+    "sbmc_conv5x5_half_supported",
+    "sbmc_conv5x5_half_weights_bytes",
+    "sbmc_conv5x5_half_prepare_weights",
+    "sbmc_conv5x5_half_pack_nchw_f32",
+    "sbmc_conv5x5_half_pack_nchw_f16",
+    "sbmc_conv5x5_half_unpack_nhwc",
+    "sbmc_conv5x5_half_bias_act_nhwc",
     "sbmc_wbank_forward_f32",
     "sbmc_wbank_backward_f32",
 )
-ABI_VERSION = 10
+ABI_VERSION = 11
 WBANK_MAX = 24
 
 
@@ -344,12 +351,20 @@ def lib():
     handle.sbmc_conv5x5_wgrad_supported.argtypes = [i] * 5
     handle.sbmc_conv5x5_wgrad_scratch_bytes.argtypes = [i] * 5
     handle.sbmc_conv5x5_wgrad_bias_f32.argtypes = [p, i, p, p, i, p, p, lg, lg, lg, lg, p, p, i, i, i, i, i, p]
+    handle.sbmc_conv5x5_half_supported.argtypes = [i] * 5
+    handle.sbmc_conv5x5_half_weights_bytes.argtypes = [i, i]
+    handle.sbmc_conv5x5_half_prepare_weights.argtypes = [p, lg, lg, lg, lg, i, i, p, p]
+    handle.sbmc_conv5x5_half_pack_nchw_f32.argtypes = [p, p, i, i, i, lg, p]
+    handle.sbmc_conv5x5_half_pack_nchw_f16.argtypes = [p, p, i, i, i, lg, p]
+    handle.sbmc_conv5x5_half_unpack_nhwc.argtypes = [p, i, p, i, i, lg, p]
+    handle.sbmc_conv5x5_half_bias_act_nhwc.argtypes = [p, i, p, p, p, i, i, i, i, i, i, ctypes.c_float, p]
     for name in SYMBOLS[2:]:
         getattr(handle, name).restype = i
     handle.sbmc_halo_bytes.restype = ctypes.c_size_t
     handle.sbmc_pointwise_wide_bwd_ws_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_weights_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv5x5_weights_bytes.restype = ctypes.c_size_t
+    handle.sbmc_conv5x5_half_weights_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv5x5_wgrad_scratch_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_workspace_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_wgrad_scratch_bytes.restype = ctypes.c_size_t

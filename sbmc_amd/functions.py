@@ -1924,6 +1924,68 @@ def conv5x5_chain(x, layers):
     return out
 
 
+def conv5x5_chain_half_supported(x, channels):
+    """Can `conv5x5_chain_half` run the chain of unpadded 5 x 5 convolutions with the channel counts `channels` on x
+    [b, cin, h, w]?  (fp32 or half on a GPU, neither SBMC_CONV5X5 nor SBMC_CONV5X5_HALF 0, every layer's shape one
+    csrc/conv5x5_half.hip takes.)"""
+    if not (x.is_cuda and x.dtype in (th.float32, th.float16) and x.dim() == 4 and x.numel() > 0 and x.shape[1] == channels[0]):
+        return False
+    if knob("SBMC_CONV5X5") == 0 or knob("SBMC_CONV5X5_HALF") == 0:
+        return False
+    L = _lib.lib()
+    b, _, h, w = (int(v) for v in x.shape)
+    for cin, cout in zip(channels[:-1], channels[1:]):
+        if not L.sbmc_conv5x5_half_supported(b, h, w, int(cin), int(cout)):
+            return False
+        h, w = h - 4, w - 4
+    return True
+
+
+def conv5x5_chain_half(x, layers):
+    """`conv5x5_chain` on HALF activations: KPCN's ConvChains (reference sbmc/models.py:221-291) under
+    torch.autocast(float16), on csrc/conv5x5_half.hip instead of the library's half solvers.  Autocast's arithmetic: x and
+    the fp32 weights rounded to half once, exact products summed in fp32, bias (fp32) and activation in fp32, every layer's
+    result rounded to half once.  INFERENCE only: the result carries no autograd graph.
+
+    x [b, cin, h, w] planar fp32 or half; layers: [(weight fp32 [cout, cin, 5, 5], bias fp32 [cout], act, slope), ...] ->
+    [b, cout, h - 4 L, w - 4 L] planar contiguous float16."""
+    if not x.is_cuda or x.dtype not in (th.float32, th.float16):
+        raise TypeError("conv5x5_chain_half: x must be a float32 or float16 GPU tensor, got %s on %s" % (x.dtype, x.device))
+    L = _lib.lib()
+    dev = x.device
+    x = x.detach().contiguous()
+    b, c, h, w = (int(v) for v in x.shape)
+    with th.cuda.device(dev), th.no_grad(), _timed("conv5x5_chain_half %dx%dx%dx%d" % (b, c, h, w), dev):
+        stream = _lib.current_stream(dev)
+        ld = L.sbmc_conv5x5_padded_channels(c)
+        buf = th.empty((b, h, w, ld), dtype=th.float16, device=dev)
+        pack = L.sbmc_conv5x5_half_pack_nchw_f32 if x.dtype == th.float32 else L.sbmc_conv5x5_half_pack_nchw_f16
+        _lib.check(pack(_lib.ptr(x), _lib.ptr(buf), ld, b, c, h * w, stream), "conv5x5_half_pack")
+        for i, (weight, bias, act, slope) in enumerate(layers):
+            _require_f32("conv5x5_chain_half", weight=weight, bias=bias)
+            cout = int(weight.shape[0])
+            if tuple(weight.shape[1:]) != (c, 5, 5) or tuple(bias.shape) != (cout,) or act not in (0, 1, 2):
+                raise ValueError("conv5x5_chain_half: layer %d takes %s, the chain has %d channels there" % (i, tuple(weight.shape), c))
+            if not L.sbmc_conv5x5_half_supported(b, h, w, c, cout):
+                raise ValueError("conv5x5_chain_half: layer %d (%d -> %d channels on %d x %d) is not supported" % (i, c, cout, h, w))
+            wt = weight.detach()
+            if not wt.is_contiguous():
+                wt = wt.contiguous()                           # (the kernel reads any strides, inside ONE dense storage)
+            s = wt.stride()
+            wp = th.empty(L.sbmc_conv5x5_half_weights_bytes(c, cout), dtype=th.uint8, device=dev)
+            _lib.check(L.sbmc_conv5x5_half_prepare_weights(_lib.ptr(wt), s[0], s[1], s[2], s[3], c, cout, _lib.ptr(wp), stream),
+                       "conv5x5_half_prepare_weights")
+            ldy = L.sbmc_conv5x5_padded_channels(cout)
+            y = th.empty((b, h - 4, w - 4, ldy), dtype=th.float16, device=dev)
+            _lib.check(L.sbmc_conv5x5_half_bias_act_nhwc(
+                _lib.ptr(buf), ld, _lib.ptr(wp), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), ldy, b, h, w, c, cout,
+                1.0 if act == 0 else (0.0 if act == 1 else float(slope)), stream), "conv5x5_half_bias_act_nhwc")
+            buf, ld, c, h, w = y, ldy, cout, h - 4, w - 4
+        out = th.empty((b, c, h, w), dtype=th.float16, device=dev)
+        _lib.check(L.sbmc_conv5x5_half_unpack_nhwc(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, stream), "conv5x5_half_unpack")
+    return out
+
+
 def conv5x5_chain_train_supported(x, channels):
     """Can `Conv5x5ChainTrain` run the chain `conv5x5_chain_supported` accepts WITH its gradients?  (SBMC_CONV5X5_TRAIN = 1
     -- the default 0 keeps training on the library --, and csrc/conv5x5_grad.hip takes every layer's shape.)"""

@@ -454,11 +454,15 @@ class ConvChain(nn.Module):
         stride 1, unpadded, with a bias; ReLU / LeakyReLU between them and linear / ReLU / LeakyReLU at the end; no
         normalisation; fp32 without autocast.  With grad mode on and anything that requires grad the chain runs as before
         (MIOpen) unless SBMC_CONV5X5_TRAIN = 1 and csrc/conv5x5_grad.hip takes every layer (functions.Conv5x5ChainTrain).
+        HALF activations -- torch.autocast(float16) on, or a half x -- run on csrc/conv5x5_half.hip
+        (functions.conv5x5_chain_half) when autograd wants nothing from the chain and SBMC_CONV5X5_HALF is not 0; with
+        gradients wanted, under any other autocast type and for what that kernel does not take they run as before.
         KPCN's two chains (reference sbmc/models.py:221-291).  -> [(weight, bias, act, slope), ...] or None."""
         first = mods[0].layer[0] if (mods and isinstance(mods[0], ConvChain._ConvBNRelu)) else (mods[0] if mods else None)
         if not isinstance(first, nn.Conv2d) or first.kernel_size != (5, 5):
             return None
-        if x.dtype != th.float32 or x.dim() != 4 or th.is_autocast_enabled():
+        half = ConvChain._conv5x5_half_wanted(x)
+        if x.dim() != 4 or (not half and (x.dtype != th.float32 or th.is_autocast_enabled())):
             return None
         plan, i = [], 0
         while i < len(mods):
@@ -485,7 +489,13 @@ class ConvChain(nn.Module):
         if i != len(mods) or [c.in_channels for c, _ in plan[1:]] != [c.out_channels for c, _ in plan[:-1]]:
             return None
         channels = [plan[0][0].in_channels] + [c.out_channels for c, _ in plan]
-        if ConvChain._conv5x5_wants_grad(x, plan):
+        if half:
+            # (fp32 parameters only, as autocast keeps them: a `.half()` model's go to the library as they are, as before)
+            if any(t.dtype != th.float32 or not t.is_cuda for c, _ in plan for t in (conv_weight(c), c.bias)):
+                return None
+            if ConvChain._conv5x5_wants_grad(x, plan) or not funcs.conv5x5_chain_half_supported(x, channels):
+                return None
+        elif ConvChain._conv5x5_wants_grad(x, plan):
             # training: only with SBMC_CONV5X5_TRAIN = 1 (default 0: the library, as before), gradient kernels for every
             # layer, and slopes >= 0 -- the activation adjoint reads the sign off the ACTIVATED value
             if any(a[1] < 0 for _, a in plan) or not funcs.conv5x5_chain_train_supported(x, channels):
@@ -493,6 +503,15 @@ class ConvChain(nn.Module):
         elif not funcs.conv5x5_chain_supported(x, channels):
             return None
         return [(conv_weight(c), c.bias, a[0], a[1]) for c, a in plan]
+
+    @staticmethod
+    def _conv5x5_half_wanted(x):
+        """Are this chain's activations half?  Under float16 autocast the library casts x and runs its half solvers: that
+        is what csrc/conv5x5_half.hip replaces.  A half x OUTSIDE autocast with fp32 parameters is newly accepted (the
+        library refuses the mixed dtypes); with half parameters `_conv5x5_plan` leaves the chain to the library."""
+        if th.is_autocast_enabled():
+            return x.dtype in (th.float32, th.float16) and th.get_autocast_dtype("cuda") == th.float16
+        return x.dtype == th.float16
 
     @staticmethod
     def _conv5x5_wants_grad(x, plan):
@@ -514,6 +533,8 @@ class ConvChain(nn.Module):
                 if th.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for wt, b, _, _ in plan for t in (wt, b))):
                     return funcs.Conv5x5ChainTrain.apply(x, tuple((a, s) for _, _, a, s in plan),
                                                          *[t for wt, b, _, _ in plan for t in (wt, b)])
+                if ConvChain._conv5x5_half_wanted(x):
+                    return funcs.conv5x5_chain_half(x, plan)
                 return funcs.conv5x5_chain(x, plan)
         gemm = self.pointwise_as_gemm and x.is_cuda
         pending = 0                                                # halo rows still to be dropped

@@ -36,11 +36,13 @@ def timeit(fn, reps, warm=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--only", default="", help="kpcn: only KPCN's 5 x 5 convolutions")
+    ap.add_argument("--only", default="", help="kpcn: only KPCN's 5 x 5 convolutions; kpcn_half: only their half form")
     args = ap.parse_args()
     dev = th.device("cuda")
     if args.only == "kpcn":
         return kpcn_convs(dev, args.reps)
+    if args.only == "kpcn_half":
+        return kpcn_half_convs(dev, args.reps)
     shapes = [("profile-script shape (bs4,c3,128x128,k21)", 4, 3, 128, 128, 21),
               ("720p (bs1,c3,1280x720,k21)", 1, 3, 720, 1280, 21)]
     for label, bs, c, h, w, k in shapes:
@@ -93,6 +95,7 @@ def main():
         th.cuda.empty_cache()
     cnn_glue(dev, args.reps)
     kpcn_convs(dev, args.reps)
+    kpcn_half_convs(dev, args.reps)
 
 
 def cnn_glue(dev, reps):
@@ -273,6 +276,96 @@ def kpcn_convs(dev, reps):
     for k, ts in res.items():
         rec = {"op": "KPCN(27) forward + radiance.sum().backward(), %s" % k, "shape": "%dx%d" % (W, H)}
         rec.update(stats(ts))
+        print(json.dumps(rec))
+
+
+def kpcn_half_convs(dev, reps):
+    """KPCN's three 5 x 5 layer shapes at 1280x720 on HALF activations: csrc/conv5x5_half.hip (bias + ReLU in its epilogue,
+    half in, half out) against F.conv2d + bias + ReLU on half tensors, ALTERNATING in one process; next to each, the fp32
+    kernel's figure of profiles/conv5x5_bench_ops.jsonl; and the whole KPCN(27) forward under no_grad +
+    torch.autocast(float16) with SBMC_CONV5X5_HALF = 0 / 1.  f16 rate: the one product per term the kernel issues on its
+    padded shape (16 on the reduction side, 128 on the output side, whole 32 x 16 tiles) against the dense f16 peak."""
+    import torch.nn.functional as nnf
+    from sbmc_amd import KPCN, _lib
+    L = _lib.lib()
+    reps = max(3, min(reps, 10))
+
+    WARM, PER = 3, 5
+
+    def timed(fns, per=PER):
+        """[name -> fn] in turn: WARM warm-up rounds, then `reps` samples of `per` launches between two events each"""
+        out = {k: [] for k in fns}
+        for r in range(reps + WARM):
+            for k, fn in fns.items():
+                a, b = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(per):
+                    fn()
+                b.record()
+                th.cuda.synchronize()
+                if r >= WARM:
+                    out[k].append(a.elapsed_time(b) / per)
+        return {k: dict(ms=round(sorted(ts)[len(ts) // 2], 4), ms_min=round(min(ts), 4), ms_max=round(max(ts), 4))
+                for k, ts in out.items()}
+
+    fp32 = {}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "conv5x5_bench_ops.jsonl")
+    if os.path.exists(path):
+        for line in open(path):
+            rec = json.loads(line)
+            if rec["op"].endswith("ReLU, conv5x5.hip"):
+                fp32[rec["op"].split(":")[0]] = rec["ms"]
+    H, W = 720, 1280
+    stream = _lib.current_stream(dev)
+    for i, cin, cout in ((0, 27, 100), (1, 100, 100), (8, 100, 441)):
+        h, w = H - 4 * i, W - 4 * i
+        x = th.randn(1, cin, h, w, device=dev).half()
+        wt = th.randn(cout, cin, 5, 5, device=dev) * (2.0 / (25 * cin)) ** 0.5
+        bias = th.randn(cout, device=dev) * 0.1
+        wh, bh = wt.half(), bias.half()
+        ldx, ldy = L.sbmc_conv5x5_padded_channels(cin), L.sbmc_conv5x5_padded_channels(cout)
+        xb = th.empty(1, h, w, ldx, dtype=th.float16, device=dev)
+        _lib.check(L.sbmc_conv5x5_half_pack_nchw_f16(_lib.ptr(x), _lib.ptr(xb), ldx, 1, cin, h * w, stream), "pack")
+        wp = th.empty(L.sbmc_conv5x5_half_weights_bytes(cin, cout), dtype=th.uint8, device=dev)
+        s = wt.stride()
+        _lib.check(L.sbmc_conv5x5_half_prepare_weights(_lib.ptr(wt), s[0], s[1], s[2], s[3], cin, cout, _lib.ptr(wp), stream),
+                   "prepare")
+        yb = th.empty(1, h - 4, w - 4, ldy, dtype=th.float16, device=dev)
+        ours = lambda: _lib.check(L.sbmc_conv5x5_half_bias_act_nhwc(
+            _lib.ptr(xb), ldx, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(yb), ldy, 1, h, w, cin, cout, 0.0, stream), "conv5x5_half")
+        res = timed({"conv5x5_half.hip": ours, "library (half)": lambda: nnf.relu_(nnf.conv2d(x, wh, bh))})
+        px = (h - 4) * (w - 4)
+        issued = 2.0 * 25 * ldx * (-(-cout // 128) * 128) * (-(-(h - 4) // 32) * 32) * (-(-(w - 4) // 16) * 16)
+        for k, st in res.items():
+            rec = {"op": "KPCN layer %d: 5x5 valid %d->%d + bias + ReLU, %s" % (i, cin, cout, k), "shape": "%dx%d" % (w, h)}
+            rec.update(st)
+            rec["true_TFLOPs"] = round(2.0 * 25 * cin * cout * px / (rec["ms"] * 1e-3) / 1e12, 1)
+            if k == "conv5x5_half.hip":
+                rec["f16_product_TFLOPs"] = round(issued / (rec["ms"] * 1e-3) / 1e12, 1)
+                rec["frac_of_f16_peak"] = round(issued / (rec["ms"] * 1e-3) / 1e12 / F16_PEAK, 4)
+                if "KPCN layer %d" % i in fp32:
+                    rec["fp32_kernel_ms_recorded"] = fp32["KPCN layer %d" % i]
+            print(json.dumps(rec))
+        del x, xb, yb, wp
+        th.cuda.empty_cache()
+    model = KPCN(27).to(dev)
+    data = {k: th.randn(1, 27, H, W, device=dev) for k in ("kpcn_diffuse_in", "kpcn_specular_in")}
+    data.update({k: th.rand(1, 3, H, W, device=dev) for k in ("kpcn_diffuse_buffer", "kpcn_specular_buffer", "kpcn_albedo")})
+
+    def forward(flag):
+        def run():
+            os.environ["SBMC_CONV5X5_HALF"] = flag
+            with th.no_grad(), th.autocast("cuda", dtype=th.float16):
+                model(data)
+        return run
+    before = os.environ.get("SBMC_CONV5X5_HALF")
+    res = timed({"SBMC_CONV5X5_HALF=1": forward("1"), "SBMC_CONV5X5_HALF=0": forward("0")}, per=1)
+    os.environ.pop("SBMC_CONV5X5_HALF")
+    if before is not None:
+        os.environ["SBMC_CONV5X5_HALF"] = before
+    for k, st in res.items():
+        rec = {"op": "KPCN(27) forward, no_grad, autocast(float16), %s" % k, "shape": "%dx%d" % (W, H)}
+        rec.update(st)
         print(json.dumps(rec))
 
 
