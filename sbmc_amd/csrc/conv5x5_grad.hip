@@ -6,10 +6,11 @@
 // (a) DATA GRADIENT with the producing layer's activation adjoint (conv5_dgrad_kernel):
 //       gx[n,y,x,ci] = act'(xsaved[n,y,x,ci]) sum_{ky,kx,co} gz[n,y-ky,x-kx,co] w[co,ci,ky,kx]
 //     is the forward's implicit GEMM over gz padded by 4 zeros each way, with the channel sides exchanged and the taps
-//     mirrored.  The plan is the forward's to the letter (16 x 16 pixels x 128 channels per workgroup, a 20 x 20 patch per
-//     16-channel chunk as two f16 planes, 40 KB weight stages in two buffers, one barrier per stage, acc / acx, operand
-//     fetches between the MFMAs); the weights are sbmc_conv5x5_prepare_weights_f32's with strides and counts exchanged,
-//     and the mirror is in the kernel: stage j reads prepared kernel row 4 - j, tap i column 4 - i.  New:
+//     mirrored.  The plan is the forward's to the letter, and so is the code: conv5_dgrad_kernel is csrc/
+//     conv5x5_gemm_body.inc (16 x 16 pixels x 128 channels per workgroup, a 20 x 20 patch per 16-channel chunk as two f16
+//     planes, 40 KB weight stages in two buffers, one barrier per stage, acc / acx, operand fetches between the MFMAs) with
+//     `Side::mirror` set; the weights are sbmc_conv5x5_prepare_weights_f32's with strides and counts exchanged,
+//     and the mirror is the body's: stage j reads prepared kernel row 4 - j, tap i column 4 - i.  This Side's own:
 //       * the patch origin (y0 - 4, x0 - 4) in gz coordinates lies above / left of the tensor for border tiles, and a
 //         row-major offset past a row's end lands in the next row, not in zeros: every patch pixel carries an in-range
 //         predicate on BOTH sides of both coordinates (the out-of-range sentinel offset otherwise); the descriptor's base
@@ -61,226 +62,14 @@ using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 
 // =====================================================================================================================
 // (a) data gradient
-struct Dgrad5Params {
-    const float* gz;         // [N, H - 4, W - 4, ldg]
-    const u32x4* wp;         // prepared weights, sides exchanged: [cin tile][cout / 16][ky][kx][plane][k half][128]
-    const float* xsaved;     // [N, H, W, ldx]: the producing layer's activated output (this layer's input); or nullptr
-    float* gx;               // [N, H, W, ldx]
-    const unsigned* gmax;    // bit pattern of max |gz|
-    const float* wscale;     // the weights' scale
-    unsigned* amax;          // raised to the bit pattern of max |gx| (a word zeroed by the caller); or nullptr
-    int N, H, W, Ho, Wo, ldg, ldx;
-    int K16;                 // chunks of 16 gz channels
-    int tiles_x, tiles_y, ncit;
-    float slope;             // act' below zero: 1 linear, 0 ReLU, else LeakyReLU
-};
-
-__global__ __launch_bounds__(256) void conv5_dgrad_kernel(Dgrad5Params p) {
-    extern __shared__ float4 c5g_lds[];
-    u32x4* As = reinterpret_cast<u32x4*>(c5g_lds);
-    u32x4* Ws = As + 2 * C5_ABUF;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = wave_id();
-    const int l31 = lane & 31, lhi = lane >> 5;
-    const int mh = wave & 1, nh = wave >> 1;
-    const int pcol = (l31 + 12 * (l31 >> 4)) & 15;       // (the forward's rotation of a block's second row)
-    const float cg = pow2_scale_of(*p.gmax);
-    const float oscale = (1.f / cg) * (1.f / *p.wscale);
-    const int nchunks = p.K16;
-
-    unsigned t = blockIdx.x;
-    const int ct = (int)(t % (unsigned)p.ncit);
-    t /= (unsigned)p.ncit;
-    const int x0 = (int)(t % (unsigned)p.tiles_x) * C5_TS;
-    t /= (unsigned)p.tiles_x;
-    const int y0 = (int)(t % (unsigned)p.tiles_y) * C5_TS;
-    const int n = (int)(t / (unsigned)p.tiles_y);
-
-    // ---- staging of a patch chunk: patch pixel (qr, qc) is gz pixel (y0 - 4 + qr, x0 - 4 + qc) ----
-    const int rbase = y0 > 4 ? y0 - 4 : 0;               // the first patch row that exists (y0 <= H - 1: rbase < Ho)
-    const long long gelems = (long long)p.N * p.Ho * p.Wo * p.ldg;
-    const long long gfirst = (((long long)n * p.Ho + rbase) * p.Wo) * p.ldg;
-    const rsrc_t rg = c5_rsrc(p.gz + gfirst, (gelems - gfirst) * 4);
-    const rsrc_t rnone = c5_rsrc(p.gz, 0);
-    u32x4 areg[C5_AROUNDS][2];
-    unsigned avoff[C5_AROUNDS];
-#pragma unroll
-    for (int j = 0; j < C5_AROUNDS; ++j) {
-        const int u = tid + 256 * j, q = u >> 1, half = u & 1;
-        const int qr = q / C5_PS, qc = q - qr * C5_PS;
-        const int gy = y0 - 4 + qr, gc = x0 - 4 + qc;
-        const bool in = u < 2 * C5_PP && gy >= 0 && gy < p.Ho && gc >= 0 && gc < p.Wo;
-        avoff[j] = in ? (unsigned)(((gy - rbase) * p.Wo + gc) * p.ldg + half * 8) * 4u : C5_OOB;
-    }
-    // (no load of the main loop sits under a branch: a request beyond the last chunk reads an empty descriptor)
-    auto issue_a = [&](int cc, bool valid) {
-        const rsrc_t r = valid ? rg : rnone;
-#pragma unroll
-        for (int j = 0; j < C5_AROUNDS; ++j)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                areg[j][i] = __builtin_amdgcn_raw_buffer_load_b128(r, avoff[j], (unsigned)cc * 64u + 16u * i, 0);
-    };
-    auto commit_a = [&](int abuf) {
-#pragma unroll
-        for (int j = 0; j < C5_AROUNDS; ++j) {
-            const int u = tid + 256 * j, q = u >> 1, half = u & 1;
-            if (u < 2 * C5_PP) {
-                u32x4 hh, ll;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const unsigned w0 = areg[j][c / 2][(2 * c) % 4];
-                    const unsigned w1 = areg[j][c / 2][(2 * c + 1) % 4];
-                    unsigned hp, lp;
-                    f16_split_pair(__builtin_bit_cast(float, w0), __builtin_bit_cast(float, w1), cg, hp, lp);
-                    hh[c] = hp;
-                    ll[c] = lp;
-                }
-                u32x4* d = As + abuf * C5_ABUF + half * C5_PR + q;
-                d[0] = hh;
-                d[2 * C5_PR] = ll;
-            }
-        }
-    };
-    // ---- a weight stage: (chunk cc, PREPARED kernel row kr) ----
-    const long long wentries = (long long)p.ncit * p.K16 * 5 * C5_WSTAGE;
-    const rsrc_t rw = c5_rsrc(p.wp, wentries * 16);
-    u32x4 wreg[C5_WROUNDS];
-    auto issue_w = [&](int cc, int kr, bool valid) {
-        const rsrc_t r = valid ? rw : rnone;
-        const unsigned block = valid ? (unsigned)((ct * p.K16 + cc) * 5 + kr) : 0u;
-#pragma unroll
-        for (int i = 0; i < C5_WROUNDS; ++i)
-            wreg[i] = __builtin_amdgcn_raw_buffer_load_b128(r, (unsigned)(tid + 256 * i) * 16u,
-                                                            block * (unsigned)(C5_WSTAGE * 16), 0);
-    };
-    auto commit_w = [&](int wbuf) {
-#pragma unroll
-        for (int i = 0; i < C5_WROUNDS; ++i) Ws[wbuf * C5_WSTAGE + tid + 256 * i] = wreg[i];
-    };
-
-    f32x16 acc[4][2], acx[4][2];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = acx[mi][ni][r] = 0.f;
-
-    struct Ops { u32x4 ah[4], al[4], bh[2], bl[2]; };
-    // tap i of a stage: the patch shifted by i entries against prepared column 4 - i
-    auto load_ops = [&](Ops& o, const u32x4* Ab, const u32x4* Wb, int i) {
-        const int kc = 4 - i;
-        o.bh[0] = Wb[kc * 512];
-        o.ah[0] = Ab[i];
-        o.bh[1] = Wb[kc * 512 + 32];
-#pragma unroll
-        for (int mi = 1; mi < 4; ++mi) o.ah[mi] = Ab[mi * 2 * C5_PS + i];
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) o.bl[ni] = Wb[kc * 512 + 256 + ni * 32];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) o.al[mi] = Ab[2 * C5_PR + mi * 2 * C5_PS + i];
-    };
-    auto mfmas = [&](const Ops& o) {
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = c5_mfma(o.ah[mi], o.bh[ni], acc[mi][ni]);
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) acx[mi][ni] = c5_mfma(o.ah[mi], o.bl[ni], acx[mi][ni]);
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) acx[mi][ni] = c5_mfma(o.al[mi], o.bh[ni], acx[mi][ni]);
-    };
-    auto interleave = [&]() {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);      // MFMA
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read
-        }
-    };
-    const u32x4* const a_lane = As + lhi * C5_PR + (mh * 8 + (l31 >> 4)) * C5_PS + pcol;
-    const u32x4* const w_lane = Ws + lhi * C5_NT + nh * 64 + l31;
-
-    // ---- prologue: chunk 0's patch and its first stage (prepared row 4) ----
-    issue_a(0, true);
-    issue_w(0, 4, true);
-    commit_a(0);
-    commit_w(0);
-    __syncthreads();
-
-    // stage s = 5 cc + j reads patch row offset j, prepared kernel row 4 - j, weight buffer s % 2 (the forward's pipeline)
-    for (int cc = 0; cc < nchunks; ++cc) {
-        const bool more = cc + 1 < nchunks;
-        const u32x4* const Ac = a_lane + (cc & 1) * C5_ABUF;
-        auto stage = [&](const int j) {
-            const int s = cc * 5 + j;
-            if (j < 4) issue_w(cc, 3 - j, true);
-            else issue_w(cc + 1, 4, more);
-            if (j == 3) issue_a(cc + 1, more);
-            const u32x4* Ab = Ac + j * C5_PS;
-            const u32x4* Wb = w_lane + (s & 1) * C5_WSTAGE;
-            Ops o0, o1;
-            load_ops(o0, Ab, Wb, 0);
-            load_ops(o1, Ab, Wb, 1);
-            mfmas(o0);
-            interleave();
-            load_ops(o0, Ab, Wb, 2);
-            mfmas(o1);
-            interleave();
-            load_ops(o1, Ab, Wb, 3);
-            mfmas(o0);
-            interleave();
-            load_ops(o0, Ab, Wb, 4);
-            mfmas(o1);
-            interleave();
-            mfmas(o0);
-            if (j == 4) commit_a((cc + 1) & 1);
-            commit_w((s + 1) & 1);
-            __syncthreads();
-        };
-        stage(0);
-        stage(1);
-        stage(2);
-        stage(3);
-        stage(4);
-    }
-
-    // ---- epilogue: scale back, act' from the saved activation, largest magnitude, masked stores ----
-    const long long xelems = (long long)p.N * p.H * p.W * p.ldx;
-    const long long xfirst = (((long long)n * p.H + y0) * p.W + x0) * p.ldx;
-    const rsrc_t rx = c5_rsrc(p.gx + xfirst, (xelems - xfirst) * 4);
-    const bool undo = p.xsaved != nullptr;
-    const rsrc_t rs = undo ? c5_rsrc(p.xsaved + xfirst, (xelems - xfirst) * 4) : rnone;
-    int ch[2];
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) ch[ni] = ct * C5_NT + nh * 64 + ni * 32 + l31;
-    unsigned amax_run = 0;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mh * 8 + mi * 2 + (r >> 3);
-            const int col = ((r & 3) + 8 * ((r >> 2) & 1) + 4 * lhi + 12 * (r >> 3)) & 15;
-            const bool ok = y0 + row < p.H && x0 + col < p.W;
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-                const bool st = ok && ch[ni] < p.ldx;
-                const unsigned voff = st ? (unsigned)((row * p.W + col) * p.ldx + ch[ni]) * 4u : C5_OOB;
-                const float saved = buf_load(rs, voff, 0);
-                float v = (acc[mi][ni][r] + acx[mi][ni][r]) * oscale;
-                v = (undo && !(saved > 0.f)) ? v * p.slope : v;
-                if (st) {
-                    const unsigned a = abits(v);
-                    amax_run = amax_run > a ? amax_run : a;
-                }
-                buf_store(v, rx, voff, 0);
-            }
-        }
-    }
-    if (p.amax) amax_publish(amax_run, p.amax);          // (wave-uniform condition; a barrier inside)
+// The data-gradient Side of the shared body: A = gz [N, H - 4, W - 4, ldg], Y = gx [N, H, W, ldx],
+// aux = the producing layer's activated output (this layer's input, Y's shape) or nullptr, the prepared weights with the
+// channel sides exchanged.  Patch pixel (qr, qc) is gz pixel (y0 - 4 + qr, x0 - 4 + qc), checked on both sides of both
+// coordinates; the descriptor's base is the first patch row that exists (y0 <= H - 1: it is a row of gz).  Stage j reads
+// prepared kernel row 4 - j, tap i column 4 - i: the mirror.
+__global__ __launch_bounds__(256) void conv5_dgrad_kernel(Conv5Params p) {
+    using Side = Conv5Dgrad;
+#include "conv5x5_gemm_body.inc"
 }
 
 // ---- g *= act'(ysaved), elementwise over a whole padded buffer, and the largest magnitude of the result: the adjoint of
@@ -567,20 +356,23 @@ static int w5_cu_count() {
     return cus;
 }
 
+// one descriptor spans the patch rows of gz from a tile's first existing one, another a tile's rows of gx / xsaved
+static bool dgrad5_strides_ok(int w, long long ldg, long long ldx) {
+    return c5_strides_ok(C5_PS + 1, w - 4, ldg, C5_TS + 1, w, ldx, 4);
+}
+// ... one row of x, another one row of gz
+static bool wgrad5_strides_ok(int w, long long ldg, long long ldx) { return c5_strides_ok(1, w, ldx, 1, w - 4, ldg, 4); }
+
 static bool dgrad5_dims_ok(int n, int h, int w, int cin, int cout) {
-    if (n < 1 || h < 5 || w < 5 || cin < 1 || cout < 1 || cin > (1 << 20) || cout > (1 << 20)) return false;
+    if (!c5_shape_ok(n, h, w, cin, cout)) return false;
     const long long ldx = c5_pad16(cin), ldg = c5_pad16(cout), ncit = (cin + C5_NT - 1) / C5_NT;
-    // byte offsets from a tile's first existing patch row of gz, and inside a tile's rows of gx / xsaved, below 2^31
-    if ((long long)(C5_PS + 1) * (w - 4) * ldg * 4 >= C5_MAXOFF || (long long)(C5_TS + 1) * w * ldx * 4 >= C5_MAXOFF) return false;
+    if (!dgrad5_strides_ok(w, ldg, ldx)) return false;
     const long long tiles = (long long)n * ((h + C5_TS - 1) / C5_TS) * ((w + C5_TS - 1) / C5_TS) * ncit;
     return tiles < 0x7FFFFFFFll && ncit * (ldg / 16) * 5 * C5_WSTAGE * 16 < C5_MAXOFF;
 }
 
 static bool wgrad5_dims_ok(int n, int h, int w, int cin, int cout) {
-    if (n < 1 || h < 5 || w < 5 || cin < 1 || cout < 1 || cin > (1 << 20) || cout > (1 << 20)) return false;
-    const long long ldx = c5_pad16(cin), ldg = c5_pad16(cout);
-    // byte offsets inside one row of x and of gz below 2^31
-    if ((long long)w * ldx * 4 >= C5_MAXOFF || (long long)(w - 4) * ldg * 4 >= C5_MAXOFF) return false;
+    if (!c5_shape_ok(n, h, w, cin, cout) || !wgrad5_strides_ok(w, c5_pad16(cout), c5_pad16(cin))) return false;
     const long long ncombo = (long long)((cout + W5_MT - 1) / W5_MT) * ((cin + W5_NT - 1) / W5_NT) * 5;
     return ncombo < 65535;
 }
@@ -607,27 +399,22 @@ extern "C" int sbmc_conv5x5_dgrad_adj_nhwc_f32(const float* gz, int ldg, const u
                                                 const float* xsaved, float slope, float* gx, int ldx, int n, int h, int w,
                                                 int cin, int cout, unsigned* amax, void* stream) {
     if (!dgrad5_dims_ok(n, h, w, cin, cout) || !gz || !gmax || !wp_swapped || !gx) return SBMC_HIP_EINVAL;
-    if (ldx < cin || ldg < cout || ldx % 16 || ldg % 16 || ldx > (1 << 20) || ldg > (1 << 20)) return SBMC_HIP_EINVAL;
+    if (!c5_ld_ok(ldx, cin) || !c5_ld_ok(ldg, cout)) return SBMC_HIP_EINVAL;
     if ((uintptr_t)gz % 16 || (uintptr_t)wp_swapped % 16 || (uintptr_t)gx % 16 || (uintptr_t)xsaved % 16 || (uintptr_t)gmax % 4 ||
         (uintptr_t)amax % 4)
         return SBMC_HIP_EINVAL;
-    if ((long long)(C5_PS + 1) * (w - 4) * ldg * 4 >= C5_MAXOFF || (long long)(C5_TS + 1) * w * ldx * 4 >= C5_MAXOFF)
-        return SBMC_HIP_EINVAL;
-    Dgrad5Params p;
-    p.gz = gz; p.wp = static_cast<const u32x4*>(wp_swapped); p.xsaved = xsaved; p.gx = gx; p.gmax = gmax;
+    if (!dgrad5_strides_ok(w, ldg, ldx)) return SBMC_HIP_EINVAL;
+    Conv5Params p;
+    // (this Side's aux: the saved activation, a whole tensor of gx's shape, or nullptr)
+    p.a = gz; p.wp = static_cast<const u32x4*>(wp_swapped); p.aux = xsaved; p.y = gx; p.amag = gmax;
     // (the weights were prepared with the sides exchanged: cout is their reduction side)
     p.wscale = reinterpret_cast<const float*>(static_cast<const char*>(wp_swapped) + sbmc_conv5x5_weights_bytes(cout, cin) - 16);
     p.amax = amax;
-    p.N = n; p.H = h; p.W = w; p.Ho = h - 4; p.Wo = w - 4; p.ldg = ldg; p.ldx = ldx;
+    p.N = n; p.Hy = h; p.Wy = w; p.Ha = h - 4; p.Wa = w - 4; p.lda = ldg; p.ldy = ldx; p.Cout = 0;      // (no bias: Cout unused)
     p.K16 = c5_pad16(cout) / 16;
-    p.tiles_x = (w + C5_TS - 1) / C5_TS; p.tiles_y = (h + C5_TS - 1) / C5_TS; p.ncit = (cin + C5_NT - 1) / C5_NT;
+    p.tiles_x = (w + C5_TS - 1) / C5_TS; p.tiles_y = (h + C5_TS - 1) / C5_TS; p.nct = (cin + C5_NT - 1) / C5_NT;
     p.slope = slope;
-    const unsigned grid = (unsigned)((long long)n * p.tiles_y * p.tiles_x * p.ncit);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv5_dgrad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)C5_LDS_BYTES);
-    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
-    hipLaunchKernelGGL(conv5_dgrad_kernel, dim3(grid), dim3(256), C5_LDS_BYTES, (hipStream_t)stream, p);
-    return (int)hipGetLastError();
+    return conv5_gemm_launch(conv5_dgrad_kernel, p, stream);
 }
 
 extern "C" int sbmc_conv5x5_act_adjoint_nhwc_f32(float* g, const float* ysaved, float slope, long elems, unsigned* amax,
@@ -657,11 +444,11 @@ extern "C" int sbmc_conv5x5_wgrad_bias_f32(const float* gz, int ldg, const unsig
                                             const unsigned* xmax, float* gw, long s_co, long s_ci, long s_ky, long s_kx,
                                             float* gb, void* scratch, int n, int h, int w, int cin, int cout, void* stream) {
     if (!wgrad5_dims_ok(n, h, w, cin, cout) || !gz || !gmax || !x || !xmax || !gw || !gb || !scratch) return SBMC_HIP_EINVAL;
-    if (ldx < cin || ldg < cout || ldx % 16 || ldg % 16 || ldx > (1 << 20) || ldg > (1 << 20)) return SBMC_HIP_EINVAL;
+    if (!c5_ld_ok(ldx, cin) || !c5_ld_ok(ldg, cout)) return SBMC_HIP_EINVAL;
     if ((uintptr_t)gz % 16 || (uintptr_t)x % 16 || (uintptr_t)scratch % 16 || (uintptr_t)gw % 4 || (uintptr_t)gb % 4 ||
         (uintptr_t)gmax % 4 || (uintptr_t)xmax % 4)
         return SBMC_HIP_EINVAL;
-    if ((long long)w * ldx * 4 >= C5_MAXOFF || (long long)(w - 4) * ldg * 4 >= C5_MAXOFF) return SBMC_HIP_EINVAL;
+    if (!wgrad5_strides_ok(w, ldg, ldx)) return SBMC_HIP_EINVAL;
     Wgrad5Params p;
     p.gz = gz; p.x = x; p.gmax = gmax; p.xmax = xmax;
     p.N = n; p.H = h; p.W = w; p.Ho = h - 4; p.Wo = w - 4; p.ldg = ldg; p.ldx = ldx;

@@ -38,9 +38,11 @@
 // occupancy 1), so the wide tile with its lower LDS traffic ships.
 // Edges: patch pixels beyond the image are buffer loads out of range (zeros), output pixels beyond it and channels from
 // ld up are masked stores; every descriptor's range ends with its tensor.  Vector stores only.
-// From conv5x5_common.hpp (written for the fp32 kernels' 16 x 16 plan) this file takes only what does not depend on the
-// pixel tile: C5_NT (128 output channels), c5_rsrc, c5_mfma, c5_pad16, C5_OOB, C5_MAXOFF and the vector types; the tile,
-// patch and stage constants are the H5_ ones below.
+// From conv5x5_common.hpp this file takes what does not depend on the fp32 kernels' 16 x 16 plan: C5_NT (128 output
+// channels), c5_rsrc, c5_mfma, c5_pad16, C5_OOB, C5_MAXOFF and the vector types; the grid decode c5_tile and the 32 x 32
+// block's lane rotation and accumulator map (c5_pcol, c5_acc_row, c5_acc_col); the prepare unit (prep5_unit), the repack
+// (repack5) and the host rules (c5_shape_ok, c5_ld_ok, c5_strides_ok).  NOT conv5x5_gemm_body.inc: the main loop below is
+// another plan, and its tile, patch and stage constants are the H5_ ones.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/sbmc_hip.h"
@@ -76,19 +78,11 @@ __global__ __launch_bounds__(256) void conv5_half_kernel(Conv5HalfParams p) {
     u32x4* Ws = As + 2 * H5_ABUF;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = wave_id();
     const int l31 = lane & 31, lhi = lane >> 5;
-    // (conv5x5.hip: row i of a 32 x 32 block is pixel (i / 16, column) of the block's 2 rows x 16 columns, the second row's
-    // lanes rotated by 4 columns: lane 16 + j reads column (j + 12) mod 16)
-    const int pcol = (l31 + 12 * (l31 >> 4)) & 15;
+    const int pcol = c5_pcol(l31);
     const int K16 = p.K16, nchunks = (K16 + 1) >> 1, nstages = K16 * 5;
 
-    // the tile: output-channel tiles of one pixel tile are neighbours in the grid
-    unsigned t = blockIdx.x;
-    const int ct = (int)(t % (unsigned)p.ncot);
-    t /= (unsigned)p.ncot;
-    const int x0 = (int)(t % (unsigned)p.tiles_x) * H5_TX;
-    t /= (unsigned)p.tiles_x;
-    const int y0 = (int)(t % (unsigned)p.tiles_y) * H5_TY;
-    const int n = (int)(t / (unsigned)p.tiles_y);
+    const C5Tile tl = c5_tile<H5_TY, H5_TX>(blockIdx.x, p.ncot, p.tiles_x, p.tiles_y);
+    const int ct = tl.ct, x0 = tl.x0, y0 = tl.y0, n = tl.n;
 
     // ---- staging of a patch chunk: 16-byte units (pixel, octet), 80 in a patch row; threads 0 .. 239 take three rows a
     // round, twelve rounds: ONE offset register, a wave-uniform step between rounds, one LDS address + immediates.
@@ -256,10 +250,8 @@ __global__ __launch_bounds__(256) void conv5_half_kernel(Conv5HalfParams p) {
     for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            // accumulator register r of a 32 x 32 block: row (r & 3) + 8 (r >> 2) + 4 (lane / 32) of the block = pixel
-            // (r >> 3, rotated column) of its 2 rows x 16 columns; output channel lane % 32
-            const int row = wave * 8 + mi * 2 + (r >> 3);
-            const int col = ((r & 3) + 8 * ((r >> 2) & 1) + 4 * lhi + 12 * (r >> 3)) & 15;
+            const int row = wave * 8 + mi * 2 + c5_acc_row(r);
+            const int col = c5_acc_col(r, lhi);
             const bool ok = y0 + row < p.Ho && x0 + col < p.Wo;
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
@@ -278,103 +270,33 @@ __global__ __launch_bounds__(256) void conv5_half_kernel(Conv5HalfParams p) {
 }
 
 // ---- weights [cout][cin][5][5] (any strides), fp32 -> half (round to nearest) in stage order, zero-padded ----
-// entry (((((ct K16 + k16) 5 + ky) 5 + kx) 2 + khalf) 128 + co holds input channels 16 k16 + 8 khalf .. + 7 of output
-// channel 128 ct + co at tap (ky, kx); channels beyond cin / cout: zeros
+// entry (((((ct K16 + k16) 5 + ky) 5 + kx) 2 + khalf) 128 + co holds the 8 values of conv5x5_common.hpp's unit
+// (ct, k16, ky, kx, khalf, co): the entries are numbered as the units are
 struct Prep5HalfParams {
-    const float* w;
-    long s_co, s_ci, s_ky, s_kx;
-    int cout, cin, K16, ncot;
+    Prep5Src src;
     u32x4* wp;
 };
 __global__ __launch_bounds__(256) void prep5_half_weights_kernel(Prep5HalfParams p) {
-    const long units = (long)p.ncot * p.K16 * 25 * 2 * C5_NT;
     const long u = (long)blockIdx.x * 256 + threadIdx.x;
-    if (u >= units) return;
-    const int co = (int)(u % C5_NT);
-    long r = u / C5_NT;
-    const int khalf = (int)(r % 2);
-    r /= 2;
-    const int kx = (int)(r % 5);
-    r /= 5;
-    const int ky = (int)(r % 5);
-    r /= 5;
-    const int k16 = (int)(r % p.K16), ct = (int)(r / p.K16);
-    const int oc = ct * C5_NT + co, ic0 = k16 * 16 + khalf * 8;
+    if (u >= prep5_units(p.src)) return;
+    const Prep5Unit t = prep5_unit(p.src, u);
     h8 v;
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
-        v[i] = (_Float16)((oc < p.cout && ic0 + i < p.cin)
-                              ? p.w[(long)oc * p.s_co + (long)(ic0 + i) * p.s_ci + ky * p.s_ky + kx * p.s_kx] : 0.f);
-    p.wp[u] = __builtin_bit_cast(u32x4, v);           // (u IS the entry index: the units are numbered in stage order)
+    for (int i = 0; i < 8; ++i) v[i] = (_Float16)t.v[i];
+    p.wp[u] = __builtin_bit_cast(u32x4, v);
 }
 
-// ---- planar [n][c][hw] (fp32 or half) -> channels-last half [n][hw][ld] with zeros in the channels from c up, and
-// channels-last half -> planar half: conv5x5.hip's tiles of 64 pixels x 32 channels through LDS ----
-template <typename S, bool TO_NHWC>
-__global__ __launch_bounds__(256) void repack5_half_kernel(const S* __restrict__ src, _Float16* __restrict__ dst, int c, int ld,
-                                                           long hw, int ctiles, long ptiles) {
-    __shared__ float tile[32][65];
-    long b = blockIdx.x;
-    const int cti = (int)(b % ctiles);
-    b /= ctiles;
-    const long pt = b % ptiles;
-    const long n = b / ptiles;
-    const long p0 = pt * 64;
-    const int c0 = cti * 32;
-    const int tid = (int)threadIdx.x;
-    if (TO_NHWC) {
-        const S* planar = src + n * (long)c * hw;
-        _Float16* nhwc = dst + n * hw * ld;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int cl = (tid >> 6) + 4 * i, px = tid & 63;
-            tile[cl][px] = (c0 + cl < c && p0 + px < hw) ? (float)planar[(long)(c0 + cl) * hw + p0 + px] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int px = (tid >> 5) + 8 * i, cl = tid & 31;
-            if (p0 + px < hw && c0 + cl < ld) nhwc[(p0 + px) * ld + c0 + cl] = (_Float16)tile[cl][px];
-        }
-    } else {
-        const S* nhwc = src + n * hw * ld;
-        _Float16* planar = dst + n * (long)c * hw;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int px = (tid >> 5) + 8 * i, cl = tid & 31;
-            tile[cl][px] = (p0 + px < hw && c0 + cl < c) ? (float)nhwc[(p0 + px) * ld + c0 + cl] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int cl = (tid >> 6) + 4 * i, px = tid & 63;
-            if (c0 + cl < c && p0 + px < hw) planar[(long)(c0 + cl) * hw + p0 + px] = (_Float16)tile[cl][px];
-        }
-    }
+// one descriptor spans a tile's patch rows of the input and its tile rows of the output
+static bool conv5_half_strides_ok(int w, long long ldx, long long ldy) {
+    return c5_strides_ok(H5_PY + 1, w, ldx, H5_TY + 1, w - 4, ldy, 2);
 }
 
 static bool conv5_half_dims_ok(int n, int h, int w, int cin, int cout) {
-    if (n < 1 || h < 5 || w < 5 || cin < 1 || cout < 1 || cin > (1 << 20) || cout > (1 << 20)) return false;
+    if (!c5_shape_ok(n, h, w, cin, cout)) return false;
     const long long ldx = c5_pad16(cin), ldy = c5_pad16(cout), ncot = (cout + C5_NT - 1) / C5_NT;
-    // byte offsets inside one tile's rows stay below 2^31 (patch rows of the input, tile rows of the output)
-    if ((long long)(H5_PY + 1) * w * ldx * 2 >= C5_MAXOFF || (long long)(H5_TY + 1) * (w - 4) * ldy * 2 >= C5_MAXOFF) return false;
+    if (!conv5_half_strides_ok(w, ldx, ldy)) return false;
     const long long tiles = (long long)n * ((h - 4 + H5_TY - 1) / H5_TY) * ((w - 4 + H5_TX - 1) / H5_TX) * ncot;
     return tiles < 0x7FFFFFFFll && ncot * (ldx / 16) * 5 * H5_WSTAGE * 16 < C5_MAXOFF;
-}
-
-template <typename S, bool TO_NHWC>
-static int repack5_half(const S* src, _Float16* dst, int ld, int n, int c, long hw, void* stream) {
-    if (n < 0 || c < 1 || hw < 0 || ld < c || ld % 16 || ld > (1 << 20)) return SBMC_HIP_EINVAL;
-    if (n == 0 || hw == 0) return 0;
-    if (!src || !dst || (uintptr_t)src % sizeof(S) || (uintptr_t)dst % 2) return SBMC_HIP_EINVAL;
-    // (the channels-last side is covered up to ld: the packing writes its zeros)
-    const int ctiles = ((TO_NHWC ? ld : c) + 31) / 32;
-    const long ptiles = (hw + 63) / 64;
-    const long long blocks = (long long)n * ptiles * ctiles;
-    if (blocks >= 0x7FFFFFFFll) return SBMC_HIP_EINVAL;
-    hipLaunchKernelGGL((repack5_half_kernel<S, TO_NHWC>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, dst, c,
-                       ld, hw, ctiles, ptiles);
-    return (int)hipGetLastError();
 }
 
 }  // namespace sbmc
@@ -394,11 +316,8 @@ extern "C" int sbmc_conv5x5_half_prepare_weights(const float* w, long s_co, long
                                                   int cout, void* wp, void* stream) {
     const size_t bytes = sbmc_conv5x5_half_weights_bytes(cin, cout);
     if (!bytes || !w || !wp || (uintptr_t)wp % 16 || (uintptr_t)w % 4) return SBMC_HIP_EINVAL;
-    Prep5HalfParams p;
-    p.w = w; p.s_co = s_co; p.s_ci = s_ci; p.s_ky = s_ky; p.s_kx = s_kx;
-    p.cout = cout; p.cin = cin; p.K16 = c5_pad16(cin) / 16; p.ncot = (cout + C5_NT - 1) / C5_NT;
-    p.wp = static_cast<u32x4*>(wp);
-    const long units = (long)(bytes / 16);
+    const Prep5HalfParams p{prep5_src(w, s_co, s_ci, s_ky, s_kx, cin, cout), static_cast<u32x4*>(wp)};
+    const long units = prep5_units(p.src);              // (= bytes / 16: one entry a unit)
     hipLaunchKernelGGL(prep5_half_weights_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
@@ -406,11 +325,10 @@ extern "C" int sbmc_conv5x5_half_prepare_weights(const float* w, long s_co, long
 extern "C" int sbmc_conv5x5_half_bias_act_nhwc(const void* x, int ldx, const void* wp, const float* bias, void* y, int ldy,
                                                 int n, int h, int w, int cin, int cout, float slope, void* stream) {
     if (!conv5_half_dims_ok(n, h, w, cin, cout) || !x || !wp || !bias || !y) return SBMC_HIP_EINVAL;
-    if (ldx < cin || ldy < cout || ldx % 16 || ldy % 16 || ldx > (1 << 20) || ldy > (1 << 20)) return SBMC_HIP_EINVAL;
+    if (!c5_ld_ok(ldx, cin) || !c5_ld_ok(ldy, cout)) return SBMC_HIP_EINVAL;
     if ((uintptr_t)x % 16 || (uintptr_t)wp % 16 || (uintptr_t)y % 16 || (uintptr_t)bias % 4) return SBMC_HIP_EINVAL;
     // (a buffer wider than the rounded channel count: the same 31-bit rule for its strides)
-    if ((long long)(H5_PY + 1) * w * ldx * 2 >= C5_MAXOFF || (long long)(H5_TY + 1) * (w - 4) * ldy * 2 >= C5_MAXOFF)
-        return SBMC_HIP_EINVAL;
+    if (!conv5_half_strides_ok(w, ldx, ldy)) return SBMC_HIP_EINVAL;
     Conv5HalfParams p;
     p.x = static_cast<const _Float16*>(x); p.wp = static_cast<const u32x4*>(wp); p.y = static_cast<_Float16*>(y);
     p.bias = bias;
@@ -427,13 +345,13 @@ extern "C" int sbmc_conv5x5_half_bias_act_nhwc(const void* x, int ldx, const voi
 }
 
 extern "C" int sbmc_conv5x5_half_pack_nchw_f32(const float* x, void* y, int ldy, int n, int c, long hw, void* stream) {
-    return repack5_half<float, true>(x, static_cast<_Float16*>(y), ldy, n, c, hw, stream);
+    return repack5<float, _Float16, true>(x, static_cast<_Float16*>(y), ldy, n, c, hw, stream);
 }
 
 extern "C" int sbmc_conv5x5_half_pack_nchw_f16(const void* x, void* y, int ldy, int n, int c, long hw, void* stream) {
-    return repack5_half<_Float16, true>(static_cast<const _Float16*>(x), static_cast<_Float16*>(y), ldy, n, c, hw, stream);
+    return repack5<_Float16, _Float16, true>(static_cast<const _Float16*>(x), static_cast<_Float16*>(y), ldy, n, c, hw, stream);
 }
 
 extern "C" int sbmc_conv5x5_half_unpack_nhwc(const void* x, int ldx, void* y, int n, int c, long hw, void* stream) {
-    return repack5_half<_Float16, false>(static_cast<const _Float16*>(x), static_cast<_Float16*>(y), ldx, n, c, hw, stream);
+    return repack5<_Float16, _Float16, false>(static_cast<const _Float16*>(x), static_cast<_Float16*>(y), ldx, n, c, hw, stream);
 }

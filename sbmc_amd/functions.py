@@ -1855,6 +1855,89 @@ class UpsampleCatNHWC(th.autograd.Function):
         return gcoarse, gleft, None, None, None
 
 
+def _conv5x5_slope(act, slope):
+    """The kernels' slope argument of an activation (act 0 linear / 1 ReLU / 2 LeakyReLU(slope)): what it multiplies a
+    negative value by."""
+    return 1.0 if act == 0 else (0.0 if act == 1 else float(slope))
+
+
+def _conv5x5_layers_supported(x, channels, *supported):
+    """Does every layer of the chain with the channel counts `channels` on x [b, cin, h, w] (4 pixels smaller each way from
+    layer to layer) pass every one of the library's `supported(b, h, w, cin, cout)` predicates?"""
+    b, _, h, w = (int(v) for v in x.shape)
+    for cin, cout in zip(channels[:-1], channels[1:]):
+        if not all(f(b, h, w, int(cin), int(cout)) for f in supported):
+            return False
+        h, w = h - 4, w - 4
+    return True
+
+
+def _conv5x5_check_layer(who, i, layer, dims, supported, train=False):
+    """Layer i = (weight, bias, act, slope) of the chain the public caller `who` runs, where the chain is `dims` = (b, c, h,
+    w): fp32 parameters of the right shapes, a known activation (with gradients: a slope the adjoint can read the sign
+    through), a shape every predicate of `supported` takes -> cout."""
+    weight, bias, act, slope = layer
+    b, c, h, w = dims
+    _require_f32(who, weight=weight, bias=bias)
+    cout = int(weight.shape[0])
+    if tuple(weight.shape[1:]) != (c, 5, 5) or tuple(bias.shape) != (cout,) or act not in (0, 1, 2) or (train and act == 2 and slope < 0):
+        raise ValueError("%s: layer %d takes %s, the chain has %d channels there" % (who, i, tuple(weight.shape), c))
+    if not all(f(b, h, w, c, cout) for f in supported):
+        raise ValueError("%s: layer %d (%d -> %d channels on %d x %d) is not supported" % (who, i, c, cout, h, w))
+    return cout
+
+
+def _conv5x5_dense(weight, align):
+    """`weight` detached, in ONE dense storage whose base is `align`-byte aligned (the prepare kernels read any strides
+    inside it)."""
+    wt = weight.detach().contiguous()
+    return wt.clone() if wt.data_ptr() % align else wt
+
+
+def _conv5x5_forward(who, x, layers, train=False):
+    """The fp32 chain forward of `conv5x5_chain` and `Conv5x5ChainTrain` (`who`: the one that names itself in errors), on
+    the current device and stream: x packed once into a channels-last buffer whose channel stride is rounded up to what the
+    kernel wants, its magnitude word from one absmax pass, then per layer validate / prepare the weights / launch, the
+    epilogue leaving the word the next layer scales by.  layers: [(weight, bias, act, slope), ...].
+    -> (the last layer's channels-last output, ld, c, h, w, saved); saved, with `train` (which also asks every layer's
+    shape of the gradient kernels): per layer its input's (buf, ld, magnitude word, c, h, w), else None -- an inference
+    chain lets go of every buffer as soon as the next layer has read it."""
+    L = _lib.lib()
+    dev = x.device
+    stream = _lib.current_stream(dev)
+    x = x.detach().contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    b, c, h, w = (int(v) for v in x.shape)
+    supported = (L.sbmc_conv5x5_supported,)
+    if train:
+        supported += (L.sbmc_conv5x5_dgrad_supported, L.sbmc_conv5x5_wgrad_supported)
+    ld = L.sbmc_conv5x5_padded_channels(c)
+    buf = th.empty((b, h, w, ld), dtype=th.float32, device=dev)
+    _lib.check(L.sbmc_conv5x5_pack_nchw_f32(_lib.ptr(x), _lib.ptr(buf), ld, b, c, h * w, stream), "conv5x5_pack")
+    xmax = Conv3x3NHWC._absmax(x)                       # (the same values: the padding is zeros)
+    words = th.zeros(max(len(layers), 1), dtype=th.int32, device=dev)
+    saved = [] if train else None
+    for i, layer in enumerate(layers):
+        cout = _conv5x5_check_layer(who, i, layer, (b, c, h, w), supported, train)
+        weight, bias, act, slope = layer
+        wt = _conv5x5_dense(weight, 16)
+        s = wt.stride()
+        wp = th.empty(L.sbmc_conv5x5_weights_bytes(c, cout), dtype=th.uint8, device=dev)
+        _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[0], s[1], s[2], s[3], wt.numel(), c, cout,
+                                                      _lib.ptr(wp), stream), "conv5x5_prepare_weights")
+        ldy = L.sbmc_conv5x5_padded_channels(cout)
+        y = th.empty((b, h - 4, w - 4, ldy), dtype=th.float32, device=dev)
+        amax = words[i:i + 1] if (train or i + 1 < len(layers)) else None
+        _lib.check(L.sbmc_conv5x5_bias_act_nhwc_f32(
+            _lib.ptr(buf), ld, _lib.ptr(xmax), _lib.ptr(wp), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), ldy,
+            b, h, w, c, cout, _conv5x5_slope(act, slope), _lib.ptr(amax), stream), "conv5x5_bias_act_nhwc")
+        if train:
+            saved.append((buf, ld, xmax, c, h, w))
+        buf, ld, xmax, c, h, w = y, ldy, amax, cout, h - 4, w - 4
+    return buf, ld, c, h, w, saved
+
+
 def conv5x5_chain_supported(x, channels):
     """Can `conv5x5_chain` run a chain of unpadded 5 x 5 convolutions with the channel counts `channels` = [cin, c1, ...,
     cout] on x [b, cin, h, w]?  (fp32 on a GPU, SBMC_CONV5X5 not 0, every layer's shape one csrc/conv5x5.hip takes.)"""
@@ -1862,13 +1945,7 @@ def conv5x5_chain_supported(x, channels):
         return False
     if knob("SBMC_CONV5X5") == 0:
         return False
-    L = _lib.lib()
-    b, _, h, w = (int(v) for v in x.shape)
-    for cin, cout in zip(channels[:-1], channels[1:]):
-        if not L.sbmc_conv5x5_supported(b, h, w, int(cin), int(cout)):
-            return False
-        h, w = h - 4, w - 4
-    return True
+    return _conv5x5_layers_supported(x, channels, _lib.lib().sbmc_conv5x5_supported)
 
 
 def conv5x5_chain(x, layers):
@@ -1886,41 +1963,12 @@ def conv5x5_chain(x, layers):
     _require_f32("conv5x5_chain", x=x)
     L = _lib.lib()
     dev = x.device
-    x = x.detach().contiguous()
-    if x.data_ptr() % 16:
-        x = x.clone()
     b, c, h, w = (int(v) for v in x.shape)
     with th.cuda.device(dev), th.no_grad(), _timed("conv5x5_chain %dx%dx%dx%d" % (b, c, h, w), dev):
-        stream = _lib.current_stream(dev)
-        ld = L.sbmc_conv5x5_padded_channels(c)
-        buf = th.empty((b, h, w, ld), dtype=th.float32, device=dev)
-        _lib.check(L.sbmc_conv5x5_pack_nchw_f32(_lib.ptr(x), _lib.ptr(buf), ld, b, c, h * w, stream), "conv5x5_pack")
-        xmax = Conv3x3NHWC._absmax(x)                       # (the same values: the padding is zeros)
-        words = th.zeros(max(len(layers), 1), dtype=th.int32, device=dev)
-        for i, (weight, bias, act, slope) in enumerate(layers):
-            _require_f32("conv5x5_chain", weight=weight, bias=bias)
-            cout = int(weight.shape[0])
-            if tuple(weight.shape[1:]) != (c, 5, 5) or tuple(bias.shape) != (cout,) or act not in (0, 1, 2):
-                raise ValueError("conv5x5_chain: layer %d takes %s, the chain has %d channels there" % (i, tuple(weight.shape), c))
-            if not L.sbmc_conv5x5_supported(b, h, w, c, cout):
-                raise ValueError("conv5x5_chain: layer %d (%d -> %d channels on %d x %d) is not supported" % (i, c, cout, h, w))
-            wt = weight.detach()
-            if wt.data_ptr() % 16 or not wt.is_contiguous():
-                wt = wt.contiguous().clone()
-            s = wt.stride()
-            wp = th.empty(L.sbmc_conv5x5_weights_bytes(c, cout), dtype=th.uint8, device=dev)
-            _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[0], s[1], s[2], s[3], wt.numel(), c, cout,
-                                                          _lib.ptr(wp), stream), "conv5x5_prepare_weights")
-            ldy = L.sbmc_conv5x5_padded_channels(cout)
-            y = th.empty((b, h - 4, w - 4, ldy), dtype=th.float32, device=dev)
-            amax = words[i:i + 1] if i + 1 < len(layers) else None
-            _lib.check(L.sbmc_conv5x5_bias_act_nhwc_f32(
-                _lib.ptr(buf), ld, _lib.ptr(xmax), _lib.ptr(wp), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), ldy,
-                b, h, w, c, cout, 1.0 if act == 0 else (0.0 if act == 1 else float(slope)), _lib.ptr(amax), stream),
-                "conv5x5_bias_act_nhwc")
-            buf, ld, xmax, c, h, w = y, ldy, amax, cout, h - 4, w - 4
+        buf, ld, c, h, w, _ = _conv5x5_forward("conv5x5_chain", x, layers)
         out = th.empty((b, c, h, w), dtype=th.float32, device=dev)
-        _lib.check(L.sbmc_conv5x5_unpack_nhwc_f32(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, stream), "conv5x5_unpack")
+        _lib.check(L.sbmc_conv5x5_unpack_nhwc_f32(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, _lib.current_stream(dev)),
+                   "conv5x5_unpack")
     return out
 
 
@@ -1932,13 +1980,7 @@ def conv5x5_chain_half_supported(x, channels):
         return False
     if knob("SBMC_CONV5X5") == 0 or knob("SBMC_CONV5X5_HALF") == 0:
         return False
-    L = _lib.lib()
-    b, _, h, w = (int(v) for v in x.shape)
-    for cin, cout in zip(channels[:-1], channels[1:]):
-        if not L.sbmc_conv5x5_half_supported(b, h, w, int(cin), int(cout)):
-            return False
-        h, w = h - 4, w - 4
-    return True
+    return _conv5x5_layers_supported(x, channels, _lib.lib().sbmc_conv5x5_half_supported)
 
 
 def conv5x5_chain_half(x, layers):
@@ -1961,16 +2003,10 @@ def conv5x5_chain_half(x, layers):
         buf = th.empty((b, h, w, ld), dtype=th.float16, device=dev)
         pack = L.sbmc_conv5x5_half_pack_nchw_f32 if x.dtype == th.float32 else L.sbmc_conv5x5_half_pack_nchw_f16
         _lib.check(pack(_lib.ptr(x), _lib.ptr(buf), ld, b, c, h * w, stream), "conv5x5_half_pack")
-        for i, (weight, bias, act, slope) in enumerate(layers):
-            _require_f32("conv5x5_chain_half", weight=weight, bias=bias)
-            cout = int(weight.shape[0])
-            if tuple(weight.shape[1:]) != (c, 5, 5) or tuple(bias.shape) != (cout,) or act not in (0, 1, 2):
-                raise ValueError("conv5x5_chain_half: layer %d takes %s, the chain has %d channels there" % (i, tuple(weight.shape), c))
-            if not L.sbmc_conv5x5_half_supported(b, h, w, c, cout):
-                raise ValueError("conv5x5_chain_half: layer %d (%d -> %d channels on %d x %d) is not supported" % (i, c, cout, h, w))
-            wt = weight.detach()
-            if not wt.is_contiguous():
-                wt = wt.contiguous()                           # (the kernel reads any strides, inside ONE dense storage)
+        for i, layer in enumerate(layers):
+            cout = _conv5x5_check_layer("conv5x5_chain_half", i, layer, (b, c, h, w), (L.sbmc_conv5x5_half_supported,))
+            weight, bias, act, slope = layer
+            wt = _conv5x5_dense(weight, 4)
             s = wt.stride()
             wp = th.empty(L.sbmc_conv5x5_half_weights_bytes(c, cout), dtype=th.uint8, device=dev)
             _lib.check(L.sbmc_conv5x5_half_prepare_weights(_lib.ptr(wt), s[0], s[1], s[2], s[3], c, cout, _lib.ptr(wp), stream),
@@ -1979,7 +2015,7 @@ def conv5x5_chain_half(x, layers):
             y = th.empty((b, h - 4, w - 4, ldy), dtype=th.float16, device=dev)
             _lib.check(L.sbmc_conv5x5_half_bias_act_nhwc(
                 _lib.ptr(buf), ld, _lib.ptr(wp), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), ldy, b, h, w, c, cout,
-                1.0 if act == 0 else (0.0 if act == 1 else float(slope)), stream), "conv5x5_half_bias_act_nhwc")
+                _conv5x5_slope(act, slope), stream), "conv5x5_half_bias_act_nhwc")
             buf, ld, c, h, w = y, ldy, cout, h - 4, w - 4
         out = th.empty((b, c, h, w), dtype=th.float16, device=dev)
         _lib.check(L.sbmc_conv5x5_half_unpack_nhwc(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, stream), "conv5x5_half_unpack")
@@ -1992,13 +2028,7 @@ def conv5x5_chain_train_supported(x, channels):
     if knob("SBMC_CONV5X5_TRAIN", 0) != 1 or not conv5x5_chain_supported(x, channels):
         return False
     L = _lib.lib()
-    b, _, h, w = (int(v) for v in x.shape)
-    for cin, cout in zip(channels[:-1], channels[1:]):
-        if not (L.sbmc_conv5x5_dgrad_supported(b, h, w, int(cin), int(cout))
-                and L.sbmc_conv5x5_wgrad_supported(b, h, w, int(cin), int(cout))):
-            return False
-        h, w = h - 4, w - 4
-    return True
+    return _conv5x5_layers_supported(x, channels, L.sbmc_conv5x5_dgrad_supported, L.sbmc_conv5x5_wgrad_supported)
 
 
 class Conv5x5ChainTrain(th.autograd.Function):
@@ -2016,56 +2046,20 @@ class Conv5x5ChainTrain(th.autograd.Function):
     magnitude word the next launches scale by.  The first layer's data gradient runs only if x requires grad."""
 
     @staticmethod
-    def _slope(act, slope):
-        return 1.0 if act == 0 else (0.0 if act == 1 else float(slope))
-
-    @staticmethod
     def forward(ctx, x, acts, *params):
         _require_f32("Conv5x5ChainTrain", x=x)
         L = _lib.lib()
         dev = x.device
-        x = x.detach().contiguous()
-        if x.data_ptr() % 16:
-            x = x.clone()
         b, c, h, w = (int(v) for v in x.shape)
         nl = len(acts)
         if len(params) != 2 * nl or nl < 1:
             raise ValueError("Conv5x5ChainTrain: %d layers, %d parameters" % (nl, len(params)))
-        saved = []                                   # per layer: (input buffer, ld, magnitude word, c, h, w)
+        layers = [(params[2 * i], params[2 * i + 1]) + tuple(acts[i]) for i in range(nl)]
         with th.cuda.device(dev), _timed("conv5x5_chain_train %dx%dx%dx%d" % (b, c, h, w), dev):
-            stream = _lib.current_stream(dev)
-            ld = L.sbmc_conv5x5_padded_channels(c)
-            buf = th.empty((b, h, w, ld), dtype=th.float32, device=dev)
-            _lib.check(L.sbmc_conv5x5_pack_nchw_f32(_lib.ptr(x), _lib.ptr(buf), ld, b, c, h * w, stream), "conv5x5_pack")
-            xmax = Conv3x3NHWC._absmax(x)
-            words = th.zeros(nl, dtype=th.int32, device=dev)
-            for i in range(nl):
-                weight, bias = params[2 * i], params[2 * i + 1]
-                act, slope = acts[i]
-                _require_f32("Conv5x5ChainTrain", weight=weight, bias=bias)
-                cout = int(weight.shape[0])
-                if tuple(weight.shape[1:]) != (c, 5, 5) or tuple(bias.shape) != (cout,) or act not in (0, 1, 2) or (act == 2 and slope < 0):
-                    raise ValueError("Conv5x5ChainTrain: layer %d takes %s, the chain has %d channels there" % (i, tuple(weight.shape), c))
-                if not (L.sbmc_conv5x5_supported(b, h, w, c, cout) and L.sbmc_conv5x5_dgrad_supported(b, h, w, c, cout)
-                        and L.sbmc_conv5x5_wgrad_supported(b, h, w, c, cout)):
-                    raise ValueError("Conv5x5ChainTrain: layer %d (%d -> %d channels on %d x %d) is not supported" % (i, c, cout, h, w))
-                wt = weight.detach()
-                if wt.data_ptr() % 16 or not wt.is_contiguous():
-                    wt = wt.contiguous().clone()
-                s = wt.stride()
-                wp = th.empty(L.sbmc_conv5x5_weights_bytes(c, cout), dtype=th.uint8, device=dev)
-                _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[0], s[1], s[2], s[3], wt.numel(), c, cout,
-                                                              _lib.ptr(wp), stream), "conv5x5_prepare_weights")
-                ldy = L.sbmc_conv5x5_padded_channels(cout)
-                y = th.empty((b, h - 4, w - 4, ldy), dtype=th.float32, device=dev)
-                amax = words[i:i + 1]
-                _lib.check(L.sbmc_conv5x5_bias_act_nhwc_f32(
-                    _lib.ptr(buf), ld, _lib.ptr(xmax), _lib.ptr(wp), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), ldy,
-                    b, h, w, c, cout, Conv5x5ChainTrain._slope(act, slope), _lib.ptr(amax), stream), "conv5x5_bias_act_nhwc")
-                saved.append((buf, ld, xmax, c, h, w))
-                buf, ld, xmax, c, h, w = y, ldy, amax, cout, h - 4, w - 4
+            buf, ld, c, h, w, saved = _conv5x5_forward("Conv5x5ChainTrain", x, layers, train=True)
             out = th.empty((b, c, h, w), dtype=th.float32, device=dev)
-            _lib.check(L.sbmc_conv5x5_unpack_nhwc_f32(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, stream), "conv5x5_unpack")
+            _lib.check(L.sbmc_conv5x5_unpack_nhwc_f32(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, _lib.current_stream(dev)),
+                       "conv5x5_unpack")
         ctx.acts, ctx.saved, ctx.batch = tuple(acts), saved, b
         ctx.last = (buf if acts[-1][0] != 0 else None, ld, c, h, w)
         ctx.save_for_backward(*params)
@@ -2092,7 +2086,7 @@ class Conv5x5ChainTrain(th.autograd.Function):
             words = th.zeros(nl + 1, dtype=th.int32, device=dev)
             if ylast is not None:
                 gmax = words[nl:nl + 1]
-                _lib.check(L.sbmc_conv5x5_act_adjoint_nhwc_f32(_lib.ptr(gz), _lib.ptr(ylast), Conv5x5ChainTrain._slope(*acts[-1]),
+                _lib.check(L.sbmc_conv5x5_act_adjoint_nhwc_f32(_lib.ptr(gz), _lib.ptr(ylast), _conv5x5_slope(*acts[-1]),
                                                                gz.numel(), _lib.ptr(gmax), stream), "conv5x5_act_adjoint")
             else:
                 gmax = Conv3x3NHWC._absmax(g)
@@ -2113,9 +2107,7 @@ class Conv5x5ChainTrain(th.autograd.Function):
                 if not need_x:
                     break
                 # the weights with the channel sides exchanged, once per backward and layer; the kernel mirrors the taps
-                wt = weight.detach()
-                if wt.data_ptr() % 16 or not wt.is_contiguous():
-                    wt = wt.contiguous().clone()
+                wt = _conv5x5_dense(weight, 16)
                 s = wt.stride()
                 wp = th.empty(L.sbmc_conv5x5_weights_bytes(cout, cin), dtype=th.uint8, device=dev)
                 _lib.check(L.sbmc_conv5x5_prepare_weights_f32(_lib.ptr(wt), s[1], s[0], s[2], s[3], wt.numel(), cout, cin,
@@ -2125,7 +2117,7 @@ class Conv5x5ChainTrain(th.autograd.Function):
                 gnext = th.empty((b, h, w, ldx), dtype=th.float32, device=dev)
                 amax = words[i:i + 1]
                 _lib.check(L.sbmc_conv5x5_dgrad_adj_nhwc_f32(
-                    _lib.ptr(gz), ldg, _lib.ptr(gmax), _lib.ptr(wp), _lib.ptr(undo), Conv5x5ChainTrain._slope(*below),
+                    _lib.ptr(gz), ldg, _lib.ptr(gmax), _lib.ptr(wp), _lib.ptr(undo), _conv5x5_slope(*below),
                     _lib.ptr(gnext), ldx, b, h, w, cin, cout, _lib.ptr(amax), stream), "conv5x5_dgrad_adj")
                 gz, ldg, gmax, cout, ho, wo = gnext, ldx, amax, cin, h, w
             else:
