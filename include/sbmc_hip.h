@@ -41,7 +41,7 @@ extern "C" {
 #define SBMC_API
 #endif
 
-#define SBMC_HIP_ABI_VERSION 11
+#define SBMC_HIP_ABI_VERSION 12
 #define SBMC_HIP_EINVAL (-1)
 /* largest channel count the fused/plain kernels take in one call */
 #define SBMC_HIP_MAX_CHANNELS 8
@@ -887,6 +887,42 @@ SBMC_API int sbmc_conv5x5_half_pack_nchw_f16(const void *x, void *y, int ldy, in
 SBMC_API int sbmc_conv5x5_half_unpack_nhwc(const void *x, int ldx, void *y, int n, int c, long hw, void *stream);
 SBMC_API int sbmc_conv5x5_half_bias_act_nhwc(const void *x, int ldx, const void *wp, const float *bias, void *y, int ldy,
                                     int n, int h, int w, int cin, int cout, float slope, void *stream);
+
+/*
+ * ABI 12 -- the gradients of that half convolution -- replace `torch.nn.Conv2d`'s backward in the reference's ConvChain as
+ * KPCN trains it (reference sbmc/models.py:221-291) under torch.autocast(float16) -- on the same channels-last _Float16
+ * buffers and arithmetic (csrc/conv5x5_half_grad.hip): half operands as they are, the fp32 weights rounded to half once,
+ * exact products summed in fp32; no scales, no magnitude words.  h, w are the layer's INPUT size everywhere; gz
+ * [n][h - 4][w - 4][ldg] is the gradient of the layer's pre-activation.
+ *   half_dgrad_supported / half_wgrad_supported: as the fp32 rules of ABI 10, on 2-byte elements
+ *   half_dgrad_adj_nhwc:  gx[n][y][x][ci] = half(act'(xsaved[n][y][x][ci]) half(sum gz[n][y - ky][x - kx][co] half(w[co][ci][ky][kx]))),
+ *                         act'(v) = v > 0 ? 1 : slope, read from the layer's saved half input (NULL: none to undo): the
+ *                         library's half gx followed by the activation's half backward, to the bit (one rounding for ReLU);
+ *                         wp_swapped: sbmc_conv5x5_half_prepare_weights(w, s_ci, s_co, s_ky, s_kx, cout, cin, ...) -- the
+ *                         channel strides and counts exchanged; the kernel mirrors the taps.  Padding channels: 0.
+ *   half_wgrad_scratch_bytes: size of the scratch half_wgrad_bias wants (0: unsupported)
+ *   half_wgrad_bias:      gw[co][ci][ky][kx] (fp32, element strides s_*) = sum gz[n][y][x][co] x[n][y + ky][x + kx][ci] and
+ *                         gb[co] (fp32) = sum gz, summed in a fixed order: the result does not depend on the run
+ *   half_pack_adj_nchw_f32 / _f16: planar fp32 / half g[n][c][hw] -> channels-last half gz[n][hw][ld] =
+ *                         half(act'(ysaved) g) with ysaved the chain's activated half output [n][hw][ld] (zeros from c up);
+ *                         half_unpack_nhwc_f32: channels-last half -> planar fp32
+ * SBMC_HIP_EINVAL for null or misaligned pointers (16 bytes for tensors, prepared weights and scratch), channel strides
+ * that are no multiple of 16 or smaller than the count, h < 5, w < 5 and offsets beyond 31 bits; nothing is launched
+ * then.  Empty problems (pack / unpack with n == 0 or hw == 0) return 0.
+ */
+SBMC_API int sbmc_conv5x5_half_dgrad_supported(int n, int h, int w, int cin, int cout);
+SBMC_API int sbmc_conv5x5_half_dgrad_adj_nhwc(const void *gz, int ldg, const void *wp_swapped, const void *xsaved, float slope,
+                                     void *gx, int ldx, int n, int h, int w, int cin, int cout, void *stream);
+SBMC_API int sbmc_conv5x5_half_wgrad_supported(int n, int h, int w, int cin, int cout);
+SBMC_API size_t sbmc_conv5x5_half_wgrad_scratch_bytes(int n, int h, int w, int cin, int cout);
+SBMC_API int sbmc_conv5x5_half_wgrad_bias(const void *gz, int ldg, const void *x, int ldx, float *gw, long s_co, long s_ci,
+                                 long s_ky, long s_kx, float *gb, void *scratch, int n, int h, int w, int cin, int cout,
+                                 void *stream);
+SBMC_API int sbmc_conv5x5_half_pack_adj_nchw_f32(const float *g, const void *ysaved, float slope, void *gz, int ld, int n,
+                                        int c, long hw, void *stream);
+SBMC_API int sbmc_conv5x5_half_pack_adj_nchw_f16(const void *g, const void *ysaved, float slope, void *gz, int ld, int n,
+                                        int c, long hw, void *stream);
+SBMC_API int sbmc_conv5x5_half_unpack_nhwc_f32(const void *x, int ldx, float *y, int n, int c, long hw, void *stream);
 
 
 /*

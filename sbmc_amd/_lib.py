@@ -153,10 +153,18 @@ SYMBOLS = (
     "sbmc_conv5x5_half_pack_nchw_f16",
     "sbmc_conv5x5_half_unpack_nhwc",
     "sbmc_conv5x5_half_bias_act_nhwc",
+    "sbmc_conv5x5_half_dgrad_supported",
+    "sbmc_conv5x5_half_dgrad_adj_nhwc",
+    "sbmc_conv5x5_half_wgrad_supported",
+    "sbmc_conv5x5_half_wgrad_scratch_bytes",
+    "sbmc_conv5x5_half_wgrad_bias",
+    "sbmc_conv5x5_half_pack_adj_nchw_f32",
+    "sbmc_conv5x5_half_pack_adj_nchw_f16",
+    "sbmc_conv5x5_half_unpack_nhwc_f32",
     "sbmc_wbank_forward_f32",
     "sbmc_wbank_backward_f32",
 )
-ABI_VERSION = 11
+ABI_VERSION = 12
 WBANK_MAX = 24
 
 
@@ -358,6 +366,14 @@ def lib():
     handle.sbmc_conv5x5_half_pack_nchw_f16.argtypes = [p, p, i, i, i, lg, p]
     handle.sbmc_conv5x5_half_unpack_nhwc.argtypes = [p, i, p, i, i, lg, p]
     handle.sbmc_conv5x5_half_bias_act_nhwc.argtypes = [p, i, p, p, p, i, i, i, i, i, i, ctypes.c_float, p]
+    handle.sbmc_conv5x5_half_dgrad_supported.argtypes = [i] * 5
+    handle.sbmc_conv5x5_half_dgrad_adj_nhwc.argtypes = [p, i, p, p, ctypes.c_float, p, i, i, i, i, i, i, p]
+    handle.sbmc_conv5x5_half_wgrad_supported.argtypes = [i] * 5
+    handle.sbmc_conv5x5_half_wgrad_scratch_bytes.argtypes = [i] * 5
+    handle.sbmc_conv5x5_half_wgrad_bias.argtypes = [p, i, p, i, p, lg, lg, lg, lg, p, p, i, i, i, i, i, p]
+    handle.sbmc_conv5x5_half_pack_adj_nchw_f32.argtypes = [p, p, ctypes.c_float, p, i, i, i, lg, p]
+    handle.sbmc_conv5x5_half_pack_adj_nchw_f16.argtypes = [p, p, ctypes.c_float, p, i, i, i, lg, p]
+    handle.sbmc_conv5x5_half_unpack_nhwc_f32.argtypes = [p, i, p, i, i, lg, p]
     for name in SYMBOLS[2:]:
         getattr(handle, name).restype = i
     handle.sbmc_halo_bytes.restype = ctypes.c_size_t
@@ -366,6 +382,7 @@ def lib():
     handle.sbmc_conv5x5_weights_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv5x5_half_weights_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv5x5_wgrad_scratch_bytes.restype = ctypes.c_size_t
+    handle.sbmc_conv5x5_half_wgrad_scratch_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_workspace_bytes.restype = ctypes.c_size_t
     handle.sbmc_conv3x3_wgrad_scratch_bytes.restype = ctypes.c_size_t
     handle.sbmc_splat_update_bwd_scratch_bytes.restype = ctypes.c_size_t

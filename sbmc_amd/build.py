@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libsbmc_hip.so")
-SOURCES = ["plain_ops.hip", "splat_fused.hip", "bias_act.hip", "pointwise.hip", "pointwise_chain.hip", "pointwise_chain_bwd.hip", "resample.hip", "nhwc_ops.hip", "halo.hip", "conv3x3.hip", "conv5x5.hip", "conv5x5_grad.hip", "conv5x5_half.hip"]
+SOURCES = ["plain_ops.hip", "splat_fused.hip", "bias_act.hip", "pointwise.hip", "pointwise_chain.hip", "pointwise_chain_bwd.hip", "resample.hip", "nhwc_ops.hip", "halo.hip", "conv3x3.hip", "conv5x5.hip", "conv5x5_grad.hip", "conv5x5_half.hip", "conv5x5_half_grad.hip"]
 ARCH = "gfx950"
 
 
@@ -54,10 +54,11 @@ def is_stale():
 
 OBJ_DIR = os.path.join(HERE, ".obj")
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
-#: per source, on top of FLAGS.  conv5x5.hip, conv5x5_grad.hip, conv5x5_half.hip: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in
+#: per source, on top of FLAGS.  The four conv5x5*.hip files: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in
 #: generated code
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"conv5x5.hip": _NO_PACKED_F32, "conv5x5_grad.hip": _NO_PACKED_F32, "conv5x5_half.hip": _NO_PACKED_F32}
+EXTRA_FLAGS = {"conv5x5.hip": _NO_PACKED_F32, "conv5x5_grad.hip": _NO_PACKED_F32, "conv5x5_half.hip": _NO_PACKED_F32,
+               "conv5x5_half_grad.hip": _NO_PACKED_F32}
 
 
 _COMPILER_ID = None

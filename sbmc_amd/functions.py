@@ -2128,6 +2128,139 @@ class Conv5x5ChainTrain(th.autograd.Function):
         return (gx, None) + tuple(grads)
 
 
+def conv5x5_chain_train_half_supported(x, channels):
+    """Can `Conv5x5ChainTrainHalf` run the chain `conv5x5_chain_half_supported` accepts WITH its gradients?
+    (SBMC_CONV5X5_TRAIN = 1 -- the default 0 keeps training on the library --, and csrc/conv5x5_half_grad.hip takes every
+    layer's shape.)"""
+    if knob("SBMC_CONV5X5_TRAIN", 0) != 1 or not conv5x5_chain_half_supported(x, channels):
+        return False
+    L = _lib.lib()
+    return _conv5x5_layers_supported(x, channels, L.sbmc_conv5x5_half_dgrad_supported, L.sbmc_conv5x5_half_wgrad_supported)
+
+
+class Conv5x5ChainTrainHalf(th.autograd.Function):
+    """`conv5x5_chain_half` with a backward: KPCN's ConvChains in training under torch.autocast(float16) (reference
+    sbmc/models.py:221-291) on csrc/conv5x5_half.hip and csrc/conv5x5_half_grad.hip -- no library convolution in either
+    direction.  Autocast's arithmetic both ways: half activations and cotangents, the fp32 weights rounded to half once,
+    fp32 sums; gx of every layer rounded to half (and once more behind a LeakyReLU slope, as the activation's half backward
+    rounds it: the chain's gradients are its layers', to the bit), the parameter gradients fp32 sums written straight into
+    fp32 tensors (the library rounds them to half first).
+
+    apply(x, acts, w0, b0, w1, b1, ...): x [b, cin, h, w] planar fp32 or half; acts: ((act, slope), ...) per layer, act 0
+    linear / 1 ReLU / 2 LeakyReLU(slope >= 0: the adjoint reads the sign off the ACTIVATED value); fp32 parameters ->
+    [b, cout, h - 4 L, w - 4 L] planar float16.
+
+    Forward: the inference loop, keeping every layer's channels-last half input (and the last layer's output where it is
+    activated).  Backward: the cotangent packed to channels-last half with the last activation's adjoint applied in the
+    same pass, then per layer from the last one weight + bias gradient in one launch and, where something below wants a
+    gradient, the data gradient with the activation adjoint of the layer below in its epilogue.  The first layer's data
+    gradient runs only if x requires grad; gx has x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, acts, *params):
+        if not x.is_cuda or x.dtype not in (th.float32, th.float16):
+            raise TypeError("Conv5x5ChainTrainHalf: x must be a float32 or float16 GPU tensor, got %s on %s" % (x.dtype, x.device))
+        L = _lib.lib()
+        dev = x.device
+        xdtype = x.dtype
+        x = x.detach().contiguous()
+        b, c, h, w = (int(v) for v in x.shape)
+        nl = len(acts)
+        if len(params) != 2 * nl or nl < 1:
+            raise ValueError("Conv5x5ChainTrainHalf: %d layers, %d parameters" % (nl, len(params)))
+        supported = (L.sbmc_conv5x5_half_supported, L.sbmc_conv5x5_half_dgrad_supported, L.sbmc_conv5x5_half_wgrad_supported)
+        saved = []
+        with th.cuda.device(dev), _timed("conv5x5_chain_train_half %dx%dx%dx%d" % (b, c, h, w), dev):
+            stream = _lib.current_stream(dev)
+            ld = L.sbmc_conv5x5_padded_channels(c)
+            buf = th.empty((b, h, w, ld), dtype=th.float16, device=dev)
+            pack = L.sbmc_conv5x5_half_pack_nchw_f32 if xdtype == th.float32 else L.sbmc_conv5x5_half_pack_nchw_f16
+            _lib.check(pack(_lib.ptr(x), _lib.ptr(buf), ld, b, c, h * w, stream), "conv5x5_half_pack")
+            for i in range(nl):
+                layer = (params[2 * i], params[2 * i + 1]) + tuple(acts[i])
+                cout = _conv5x5_check_layer("Conv5x5ChainTrainHalf", i, layer, (b, c, h, w), supported, train=True)
+                weight, bias, act, slope = layer
+                wt = _conv5x5_dense(weight, 4)
+                s = wt.stride()
+                wp = th.empty(L.sbmc_conv5x5_half_weights_bytes(c, cout), dtype=th.uint8, device=dev)
+                _lib.check(L.sbmc_conv5x5_half_prepare_weights(_lib.ptr(wt), s[0], s[1], s[2], s[3], c, cout, _lib.ptr(wp), stream),
+                           "conv5x5_half_prepare_weights")
+                ldy = L.sbmc_conv5x5_padded_channels(cout)
+                y = th.empty((b, h - 4, w - 4, ldy), dtype=th.float16, device=dev)
+                _lib.check(L.sbmc_conv5x5_half_bias_act_nhwc(
+                    _lib.ptr(buf), ld, _lib.ptr(wp), _lib.ptr(bias.detach().contiguous()), _lib.ptr(y), ldy, b, h, w, c, cout,
+                    _conv5x5_slope(act, slope), stream), "conv5x5_half_bias_act_nhwc")
+                saved.append((buf, ld, c, h, w))
+                buf, ld, c, h, w = y, ldy, cout, h - 4, w - 4
+            out = th.empty((b, c, h, w), dtype=th.float16, device=dev)
+            _lib.check(L.sbmc_conv5x5_half_unpack_nhwc(_lib.ptr(buf), ld, _lib.ptr(out), b, c, h * w, stream), "conv5x5_half_unpack")
+        ctx.acts, ctx.saved, ctx.batch, ctx.xdtype = tuple(acts), saved, b, xdtype
+        ctx.last = (buf if acts[-1][0] != 0 else None, ld, c, h, w)
+        ctx.save_for_backward(*params)
+        return out
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, g):
+        L = _lib.lib()
+        params, acts, saved, b = ctx.saved_tensors, ctx.acts, ctx.saved, ctx.batch
+        ylast, ldg, cout, ho, wo = ctx.last
+        dev = g.device
+        if not g.is_cuda or g.dtype not in (th.float32, th.float16):
+            raise TypeError("Conv5x5ChainTrainHalf.backward: a float32 or float16 GPU cotangent, got %s on %s" % (g.dtype, g.device))
+        g = g.contiguous()
+        f32 = g.dtype == th.float32
+        nl = len(acts)
+        grads = [None] * (2 * nl)
+        gx = None
+        with th.cuda.device(dev), _timed("conv5x5_chain_train_half_bwd %dx%dx%dx%d" % (b, cout, ho, wo), dev):
+            stream = _lib.current_stream(dev)
+            gz = th.empty((b, ho, wo, ldg), dtype=th.float16, device=dev)
+            if ylast is not None:
+                pack = L.sbmc_conv5x5_half_pack_adj_nchw_f32 if f32 else L.sbmc_conv5x5_half_pack_adj_nchw_f16
+                _lib.check(pack(_lib.ptr(g), _lib.ptr(ylast), _conv5x5_slope(*acts[-1]), _lib.ptr(gz), ldg, b, cout, ho * wo,
+                                stream), "conv5x5_half_pack_adj")
+            else:
+                pack = L.sbmc_conv5x5_half_pack_nchw_f32 if f32 else L.sbmc_conv5x5_half_pack_nchw_f16
+                _lib.check(pack(_lib.ptr(g), _lib.ptr(gz), ldg, b, cout, ho * wo, stream), "conv5x5_half_pack")
+            for i in range(nl - 1, -1, -1):
+                xin, ldx, cin, h, w = saved[i]
+                weight = params[2 * i]
+                need_w = ctx.needs_input_grad[2 + 2 * i] or ctx.needs_input_grad[3 + 2 * i]
+                need_x = ctx.needs_input_grad[0] or any(ctx.needs_input_grad[2:2 + 2 * i])
+                if need_w:
+                    gw = th.empty(weight.shape, dtype=th.float32, device=dev)
+                    gb = th.empty(cout, dtype=th.float32, device=dev)
+                    scratch = th.empty(L.sbmc_conv5x5_half_wgrad_scratch_bytes(b, h, w, cin, cout), dtype=th.uint8, device=dev)
+                    s = gw.stride()
+                    _lib.check(L.sbmc_conv5x5_half_wgrad_bias(
+                        _lib.ptr(gz), ldg, _lib.ptr(xin), ldx, _lib.ptr(gw), s[0], s[1], s[2], s[3], _lib.ptr(gb),
+                        _lib.ptr(scratch), b, h, w, cin, cout, stream), "conv5x5_half_wgrad_bias")
+                    grads[2 * i], grads[2 * i + 1] = gw, gb
+                if not need_x:
+                    break
+                # the weights with the channel sides exchanged, once per backward and layer; the kernel mirrors the taps
+                wt = _conv5x5_dense(weight, 4)
+                s = wt.stride()
+                wp = th.empty(L.sbmc_conv5x5_half_weights_bytes(cout, cin), dtype=th.uint8, device=dev)
+                _lib.check(L.sbmc_conv5x5_half_prepare_weights(_lib.ptr(wt), s[1], s[0], s[2], s[3], cout, cin, _lib.ptr(wp), stream),
+                           "conv5x5_half_prepare_weights")
+                below = acts[i - 1] if i > 0 else (0, 1.0)
+                undo = xin if below[0] != 0 else None
+                gnext = th.empty((b, h, w, ldx), dtype=th.float16, device=dev)
+                _lib.check(L.sbmc_conv5x5_half_dgrad_adj_nhwc(
+                    _lib.ptr(gz), ldg, _lib.ptr(wp), _lib.ptr(undo), _conv5x5_slope(*below), _lib.ptr(gnext), ldx,
+                    b, h, w, cin, cout, stream), "conv5x5_half_dgrad_adj")
+                gz, ldg, cout, ho, wo = gnext, ldx, cin, h, w
+            else:
+                if ctx.needs_input_grad[0]:
+                    gx = th.empty((b, cout, ho, wo), dtype=ctx.xdtype, device=dev)
+                    unpack = L.sbmc_conv5x5_half_unpack_nhwc_f32 if ctx.xdtype == th.float32 else L.sbmc_conv5x5_half_unpack_nhwc
+                    _lib.check(unpack(_lib.ptr(gz), ldg, _lib.ptr(gx), b, cout, ho * wo, stream), "conv5x5_half_unpack")
+        grads = [gr if ctx.needs_input_grad[2 + k] else None for k, gr in enumerate(grads)]
+        return (gx, None) + tuple(grads)
+
+
 def gather_update_supported(data, kernels):
     """True when the fused gather-kernel update (`SplatUpdate(..., gather=True)`) applies."""
     if not (data.is_cuda and kernels.is_cuda) or data.dtype != th.float32 or kernels.dtype != th.float32:

@@ -455,8 +455,9 @@ class ConvChain(nn.Module):
         normalisation; fp32 without autocast.  With grad mode on and anything that requires grad the chain runs as before
         (MIOpen) unless SBMC_CONV5X5_TRAIN = 1 and csrc/conv5x5_grad.hip takes every layer (functions.Conv5x5ChainTrain).
         HALF activations -- torch.autocast(float16) on, or a half x -- run on csrc/conv5x5_half.hip
-        (functions.conv5x5_chain_half) when autograd wants nothing from the chain and SBMC_CONV5X5_HALF is not 0; with
-        gradients wanted, under any other autocast type and for what that kernel does not take they run as before.
+        (functions.conv5x5_chain_half) when SBMC_CONV5X5_HALF is not 0 -- with gradients wanted only if SBMC_CONV5X5_TRAIN = 1
+        as well and csrc/conv5x5_half_grad.hip takes every layer (functions.Conv5x5ChainTrainHalf); under any other
+        autocast type and for what those kernels do not take they run as before.
         KPCN's two chains (reference sbmc/models.py:221-291).  -> [(weight, bias, act, slope), ...] or None."""
         first = mods[0].layer[0] if (mods and isinstance(mods[0], ConvChain._ConvBNRelu)) else (mods[0] if mods else None)
         if not isinstance(first, nn.Conv2d) or first.kernel_size != (5, 5):
@@ -493,7 +494,11 @@ class ConvChain(nn.Module):
             # (fp32 parameters only, as autocast keeps them: a `.half()` model's go to the library as they are, as before)
             if any(t.dtype != th.float32 or not t.is_cuda for c, _ in plan for t in (conv_weight(c), c.bias)):
                 return None
-            if ConvChain._conv5x5_wants_grad(x, plan) or not funcs.conv5x5_chain_half_supported(x, channels):
+            if ConvChain._conv5x5_wants_grad(x, plan):
+                # training under float16 autocast: as the fp32 rule below, on csrc/conv5x5_half_grad.hip
+                if any(a[1] < 0 for _, a in plan) or not funcs.conv5x5_chain_train_half_supported(x, channels):
+                    return None
+            elif not funcs.conv5x5_chain_half_supported(x, channels):
                 return None
         elif ConvChain._conv5x5_wants_grad(x, plan):
             # training: only with SBMC_CONV5X5_TRAIN = 1 (default 0: the library, as before), gradient kernels for every
@@ -531,8 +536,8 @@ class ConvChain(nn.Module):
             plan = ConvChain._conv5x5_plan(mods, x)
             if plan is not None:
                 if th.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for wt, b, _, _ in plan for t in (wt, b))):
-                    return funcs.Conv5x5ChainTrain.apply(x, tuple((a, s) for _, _, a, s in plan),
-                                                         *[t for wt, b, _, _ in plan for t in (wt, b)])
+                    train = funcs.Conv5x5ChainTrainHalf if ConvChain._conv5x5_half_wanted(x) else funcs.Conv5x5ChainTrain
+                    return train.apply(x, tuple((a, s) for _, _, a, s in plan), *[t for wt, b, _, _ in plan for t in (wt, b)])
                 if ConvChain._conv5x5_half_wanted(x):
                     return funcs.conv5x5_chain_half(x, plan)
                 return funcs.conv5x5_chain(x, plan)

@@ -36,13 +36,16 @@ def timeit(fn, reps, warm=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--only", default="", help="kpcn: only KPCN's 5 x 5 convolutions; kpcn_half: only their half form")
+    ap.add_argument("--only", default="", help="kpcn: only KPCN's 5 x 5 convolutions; kpcn_half: only their half form; "
+                                                "kpcn_half_grad: only the half form's gradients")
     args = ap.parse_args()
     dev = th.device("cuda")
     if args.only == "kpcn":
         return kpcn_convs(dev, args.reps)
     if args.only == "kpcn_half":
         return kpcn_half_convs(dev, args.reps)
+    if args.only == "kpcn_half_grad":
+        return kpcn_half_grad_convs(dev, args.reps)
     shapes = [("profile-script shape (bs4,c3,128x128,k21)", 4, 3, 128, 128, 21),
               ("720p (bs1,c3,1280x720,k21)", 1, 3, 720, 1280, 21)]
     for label, bs, c, h, w, k in shapes:
@@ -367,6 +370,111 @@ def kpcn_half_convs(dev, reps):
         rec = {"op": "KPCN(27) forward, no_grad, autocast(float16), %s" % k, "shape": "%dx%d" % (W, H)}
         rec.update(st)
         print(json.dumps(rec))
+
+
+def kpcn_half_grad_convs(dev, reps):
+    """The gradients of KPCN's three 5 x 5 layer shapes at 1280x720 on HALF activations: the data gradient and the weight +
+    bias gradient of csrc/conv5x5_half_grad.hip against torch.autograd.grad of F.conv2d on half tensors (the library's half
+    backward: what SBMC_CONV5X5_TRAIN = 0 runs under autocast), ALTERNATING in one process; next to each, the fp32
+    kernel's figure of profiles/conv5x5_grad_bench_ops.jsonl; and the whole KPCN(27) forward + backward under
+    torch.autocast(float16) with SBMC_CONV5X5_TRAIN = 0 / 1.  f16 rate: the one product per term the kernels issue on their
+    padded shapes (dgrad: 16 gz channels, 128 x channels, whole 32 x 16 tiles; wgrad: 128 x 64 channel tiles, 25 taps, 32-pixel
+    row stages) against the dense f16 peak."""
+    import torch.nn.functional as nnf
+    from sbmc_amd import KPCN, _lib
+    L = _lib.lib()
+    reps = max(3, min(reps, 10))
+    WARM = 2
+
+    def timed(fns):
+        """[name -> fn] in turn: WARM warm-up rounds, then `reps` samples of one launch between two events each"""
+        out = {k: [] for k in fns}
+        for r in range(reps + WARM):
+            for k, fn in fns.items():
+                a, b = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                th.cuda.synchronize()
+                if r >= WARM:
+                    out[k].append(a.elapsed_time(b))
+        return {k: dict(ms=round(sorted(ts)[len(ts) // 2], 4), ms_min=round(min(ts), 4), ms_max=round(max(ts), 4))
+                for k, ts in out.items()}
+
+    fp32 = {}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "conv5x5_grad_bench_ops.jsonl")
+    if os.path.exists(path):
+        for line in open(path):
+            rec = json.loads(line)
+            if rec["op"].endswith("conv5x5_grad.hip"):
+                fp32[rec["op"].replace("conv5x5_grad.hip", "conv5x5_half_grad.hip")] = rec["ms"]
+    H, W = 720, 1280
+    stream = _lib.current_stream(dev)
+    for i, cin, cout in ((0, 27, 100), (1, 100, 100), (8, 100, 441)):
+        h, w = H - 4 * i, W - 4 * i
+        px = (h - 4) * (w - 4)
+        x = th.randn(1, cin, h, w, device=dev).half()
+        wt = th.randn(cout, cin, 5, 5, device=dev) * (2.0 / (25 * cin)) ** 0.5
+        gz = th.randn(1, cout, h - 4, w - 4, device=dev).half()
+        ldx, ldg = L.sbmc_conv5x5_padded_channels(cin), L.sbmc_conv5x5_padded_channels(cout)
+        xb = th.empty(1, h, w, ldx, dtype=th.float16, device=dev)
+        gzb = th.empty(1, h - 4, w - 4, ldg, dtype=th.float16, device=dev)
+        _lib.check(L.sbmc_conv5x5_half_pack_nchw_f16(_lib.ptr(x), _lib.ptr(xb), ldx, 1, cin, h * w, stream), "pack")
+        _lib.check(L.sbmc_conv5x5_half_pack_nchw_f16(_lib.ptr(gz), _lib.ptr(gzb), ldg, 1, cout, px, stream), "pack")
+        s = wt.stride()
+        wps = th.empty(L.sbmc_conv5x5_half_weights_bytes(cout, cin), dtype=th.uint8, device=dev)
+        _lib.check(L.sbmc_conv5x5_half_prepare_weights(_lib.ptr(wt), s[1], s[0], s[2], s[3], cout, cin, _lib.ptr(wps), stream),
+                   "prepare")
+        gxb, gw, gb = th.empty_like(xb), th.empty_like(wt), th.empty(cout, device=dev)
+        scratch = th.empty(L.sbmc_conv5x5_half_wgrad_scratch_bytes(1, h, w, cin, cout), dtype=th.uint8, device=dev)
+        xr, wr = x.clone().requires_grad_(), wt.half().requires_grad_()
+        yl = nnf.conv2d(xr, wr)
+        res = timed({
+            "dgrad, conv5x5_half_grad.hip": lambda: _lib.check(L.sbmc_conv5x5_half_dgrad_adj_nhwc(
+                _lib.ptr(gzb), ldg, _lib.ptr(wps), _lib.ptr(xb), 0.0, _lib.ptr(gxb), ldx, 1, h, w, cin, cout, stream), "dgrad"),
+            "dgrad, library (half)": lambda: th.autograd.grad(yl, xr, gz, retain_graph=True),
+            "wgrad + bias, conv5x5_half_grad.hip": lambda: _lib.check(L.sbmc_conv5x5_half_wgrad_bias(
+                _lib.ptr(gzb), ldg, _lib.ptr(xb), ldx, _lib.ptr(gw), s[0], s[1], s[2], s[3], _lib.ptr(gb), _lib.ptr(scratch),
+                1, h, w, cin, cout, stream), "wgrad"),
+            "wgrad, library (half)": lambda: th.autograd.grad(yl, wr, gz, retain_graph=True)})
+        issued = {
+            "dgrad": 2.0 * 25 * ldg * (-(-cin // 128) * 128) * (-(-h // 32) * 32) * (-(-w // 16) * 16),
+            "wgrad": 2.0 * 25 * (-(-cout // 128) * 128) * (-(-cin // 64) * 64) * (h - 4) * (-(-(w - 4) // 32) * 32)}
+        for k, st in res.items():
+            rec = {"op": "KPCN layer %d: 5x5 valid %d->%d %s" % (i, cin, cout, k), "shape": "%dx%d" % (w, h)}
+            rec.update(st)
+            rec["true_TFLOPs"] = round(2.0 * 25 * cin * cout * px / (rec["ms"] * 1e-3) / 1e12, 1)
+            if k.endswith("conv5x5_half_grad.hip"):
+                n = issued[k[:5]]
+                rec["f16_product_TFLOPs"] = round(n / (rec["ms"] * 1e-3) / 1e12, 1)
+                rec["frac_of_f16_peak"] = round(n / (rec["ms"] * 1e-3) / 1e12 / F16_PEAK, 4)
+                rec["ratio_to_library"] = round(res[k[:5] + ", library (half)"]["ms"] / rec["ms"], 2)
+                if rec["op"] in fp32:
+                    rec["fp32_kernel_ms_recorded"] = fp32[rec["op"]]
+            print(json.dumps(rec), flush=True)
+        del x, xb, gz, gzb, wps, gxb, scratch, xr, wr, yl
+        th.cuda.empty_cache()
+    model = KPCN(27).to(dev)
+    data = {k: th.randn(1, 27, H, W, device=dev) for k in ("kpcn_diffuse_in", "kpcn_specular_in")}
+    data.update({k: th.rand(1, 3, H, W, device=dev) for k in ("kpcn_diffuse_buffer", "kpcn_specular_buffer", "kpcn_albedo")})
+
+    def train(flag):
+        def run():
+            os.environ["SBMC_CONV5X5_TRAIN"] = flag
+            model.zero_grad(set_to_none=True)
+            with th.autocast("cuda", dtype=th.float16):
+                out = model(data)["radiance"]
+            out.float().sum().backward()
+        return run
+    before = os.environ.get("SBMC_CONV5X5_TRAIN")
+    res = timed({"SBMC_CONV5X5_TRAIN=1": train("1"), "SBMC_CONV5X5_TRAIN=0": train("0")})
+    os.environ.pop("SBMC_CONV5X5_TRAIN")
+    if before is not None:
+        os.environ["SBMC_CONV5X5_TRAIN"] = before
+    for k, st in res.items():
+        rec = {"op": "KPCN(27) forward + radiance.sum().backward(), autocast(float16), %s" % k, "shape": "%dx%d" % (W, H)}
+        rec.update(st)
+        print(json.dumps(rec), flush=True)
 
 
 if __name__ == "__main__":
